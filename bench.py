@@ -9,6 +9,15 @@ already resident in HBM (grid and points uploaded before the timed region);
 the step includes every device launch, the device->host score copies and the
 host finish (std::sort / FindBestCandidate / covariance) of all windows.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times
+exactly K steps and prints the headline line (value, ms_per_step); with
+`--dump-outputs DIR` it also writes the last timed step's scores, poses and
+covariances to DIR/<name>.npy (the inputs are seeded: the same arguments give
+the same inputs, so two builds compare output for output). Everything below
+that takes runs of its own (per-kernel breakdown and roofline, latency probe,
+host-input batches, the B=109 line, the config-3 RCCL leg, CPU baselines,
+parity against the oracle) runs with `--full` only.
+
 Multi-GPU: one process per GPU; each rank matches its own batch (weak scaling,
 no data-path collective — independent scans). Timing: barrier +
 synchronize on both sides of exactly --steps steps, max over ranks.
@@ -669,6 +678,26 @@ def plumbing_bench(args, rank, world_size, dist, torch):
                      "kernels": kernels}}
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(dirname: str, final, rank: int, world_size: int) -> None:
+    """--dump-outputs: the last timed step's (scores, poses, covs), what a
+    caller of the timed path receives, as <name>.npy in float64 (rank 0;
+    the other ranks' files carry _rank<r>). All ranks together stay under
+    DUMP_BUDGET_BYTES: a larger batch is cut to a fixed, seeded sample of its
+    scans (the same rows in every array, in ascending order)."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = [np.asarray(a, dtype=np.float64).reshape(len(final[0]), -1) for a in final]
+    n = arrays[0].shape[0]
+    cap = DUMP_BUDGET_BYTES // (8 * sum(a.shape[1] for a in arrays) * world_size)
+    rows = np.sort(np.random.default_rng(20261015).choice(n, cap, replace=False)) if n > cap else None
+    sfx = "" if rank == 0 else f"_rank{rank}"
+    for name, a in zip(("scores", "poses", "covs"), arrays):
+        a = a if rows is None else a[rows]
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), np.ascontiguousarray(a[:, 0] if name == "scores" else a))
+
+
 def build_info() -> dict:
     """Which library ran: the source digest compiled into it (csm_build_digest)
     against the tree's sources (a stale prebuilt .so shows match: false)."""
@@ -790,10 +819,23 @@ def main():
                     help="config2: skip the reference-default B=109 (U=100) line beside the headline")
     ap.add_argument("--backend", choices=["auto", "nccl", "gloo"], default="auto",
                     help="torch.distributed backend (auto: nccl = RCCL on a GPU box, gloo on CPU)")
-    ap.add_argument("--detail-json", default=DETAIL_JSON,
+    ap.add_argument("--detail-json", default=None,
                     help="config2 / plumbing: the whole result (per-kernel tables, breakdowns) goes here; "
-                         "the last stdout line is the compact headline ('' = no side file)")
+                         "the last stdout line is the compact headline ('' = no side file; default: "
+                         f"{DETAIL_JSON} with --full and for plumbing, none for a plain config2 run)")
+    ap.add_argument("--full", action="store_true",
+                    help="config2: after the timed steps also run every other leg (per-kernel breakdown and "
+                         "roofline, single-scan latency, host-input batches, the B=109 line, the config-3 RCCL "
+                         "leg, CPU baselines and the parity check against the oracle); the --no-* options leave "
+                         "single legs out. Without it a config2 run only sets up, warms up, times --steps steps "
+                         "and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="config2: write the last timed step's scores, poses and covariances to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "config2":
+        ap.error("--dump-outputs is for --workload config2")
+    if args.detail_json is None:
+        args.detail_json = DETAIL_JSON if (args.full or args.workload != "config2") else ""
     if args.steps is None:
         args.steps = 30 if args.workload == "config2" else 5
     if args.warmup is None:
@@ -818,7 +860,7 @@ def main():
     # the config-3 RCCL leg, before this process makes any GPU call (the child
     # drives every device; the other ranks wait in the rendezvous below)
     leg = None
-    if rank == 0 and ((args.workload == "config2" and not args.no_lc_leg) or
+    if rank == 0 and ((args.workload == "config2" and args.full and not args.no_lc_leg) or
                       (args.workload == "plumbing" and args.lc_leg)):
         leg = lc_leg(args)
     local_rank = _device()
@@ -925,11 +967,9 @@ def main():
     # (CSM_BENCH_EVENTS=1 times every launch inside the value's region, as r05's first builds did)
     ev_mode = 0 if os.environ.get("CSM_BENCH_NO_EVENTS") == "1" else int(os.environ.get("CSM_BENCH_EVENTS", "2"))
     elapsed, stats_value, final = timed(levels, args.warmup, args.steps, ev_mode)
-    # the per-kernel breakdown: the same steps once more, every launch timed
-    # (its events add ~50 us of kernel-stream gaps a step, so not in `value`)
-    el_all, stats, _ = timed(levels, 5, args.steps, 1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, final, rank, world_size)
     poses = final[1]
-    poses_resident = poses.copy()
 
     per_scan = sum(_window_cands(l) for l in levels)
     local_scorings = float(args.scans * per_scan * args.steps)
@@ -943,6 +983,61 @@ def main():
         elapsed, total_scorings = float(e.item()), float(s.item())
     else:
         total_scorings = local_scorings
+
+    def headline() -> dict:
+        """The result's headline keys and the timed configuration."""
+        return {
+            "metric": METRIC,
+            "value": total_scorings / elapsed,
+            "unit": "scorings/s",
+            "n_gpus": world_size,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic (seeded 2000x2000 @5cm wall map with the reference's blur splat; "
+                    "ray-cast 1081-beam Hokuyo scans at distinct poses)",
+            "config": {
+                "workload": "config2: 1081-beam scans vs 2000x2000 @5cm fp32 grid, full 3-level "
+                            "coarse->fine->super-fine (sim-YAML windows 5070+1331+189 candidates/scan)",
+                "levels": args.levels,
+                "beams_summed": _beams_summed(batch.offsets, levels[0].use_point_size),
+                "scans_per_gpu": args.scans,
+                "scorings_per_scan": per_scan,
+                "parallelism": f"replicas x{world_size} (scan-sharded, no collective)",
+                "batches": ("one csm_scan_matchers_loaded call per step" if args.sync_steps else
+                            "submitted back to back (csm_scan_matchers_submit): step k + 1's first launch goes "
+                            "out before step k's last level is completed; every step is one whole batch, the "
+                            "timed region ends when the last one is complete"),
+                "inputs": "grid and scans resident in HBM before the timed region (csm_load_scans); the "
+                          f"host-buffer entry points add one H2D copy of the points: "
+                          f"{batch.points_cells.nbytes / 1e6:.1f} MB per step here, timed with --full as h2d_ms",
+            },
+        }
+
+    if not args.full:
+        # a plain run ends here: the headline figure and nothing that takes a
+        # run of its own (--full: breakdown, roofline, other legs, CPU baselines, parity)
+        if rank == 0:
+            out = headline()
+            out["median_pose_error_m"] = float(np.median(np.hypot(*(poses[:, :2] - batch.true_poses[:, :2]).T)))
+            out["full"] = False
+            out["host_threads"] = host
+            out["world"] = world_info(dist)
+            out["build"] = build_info()
+            emit(out, args.detail_json or None)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # the per-kernel breakdown: the same steps once more, every launch timed
+    # (its events add ~50 us of kernel-stream gaps a step, so not in `value`)
+    el_all, stats, _ = timed(levels, 5, args.steps, 1)
+    poses_resident = poses.copy()
 
     # single-scan latency (front-end, config 5 shape): one 3-level match
     lat = []
@@ -1080,35 +1175,7 @@ def main():
 
     err = np.hypot(*(poses[:, :2] - batch.true_poses[:, :2]).T)
     out = {
-        "metric": METRIC,
-        "value": total_scorings / elapsed,
-        "unit": "scorings/s",
-        "n_gpus": world_size,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (seeded 2000x2000 @5cm wall map with the reference's blur splat; "
-                "ray-cast 1081-beam Hokuyo scans at distinct poses)",
-        "config": {
-            "workload": "config2: 1081-beam scans vs 2000x2000 @5cm fp32 grid, full 3-level "
-                        "coarse->fine->super-fine (sim-YAML windows 5070+1331+189 candidates/scan)",
-            "levels": args.levels,
-            "beams_summed": _beams_summed(batch.offsets, levels[0].use_point_size),
-            "scans_per_gpu": args.scans,
-            "scorings_per_scan": per_scan,
-            "parallelism": f"replicas x{world_size} (scan-sharded, no collective)",
-            "batches": ("one csm_scan_matchers_loaded call per step" if args.sync_steps else
-                        "submitted back to back (csm_scan_matchers_submit): step k + 1's first launch goes out "
-                        "before step k's last level is completed; every step is one whole batch, the timed "
-                        "region ends when the last one is complete"),
-            "inputs": "grid and scans resident in HBM before the timed region (csm_load_scans); the "
-                      f"host-buffer entry points add one H2D copy of the points: "
-                      f"{batch.points_cells.nbytes / 1e6:.1f} MB per step here, timed below as h2d_ms",
-        },
+        **headline(),
         "roofline": rl,
         **acct,
         "single_scan_latency_ms": float(np.median(lat) * 1e3) if lat else None,
@@ -1117,6 +1184,7 @@ def main():
         "kernels_timed_region": stats_value,
     }
     out["h2d_ms"] = h2d_ms
+    out["full"] = True
     if host_inputs is not None:
         out["value_host_inputs"] = host_inputs
     out["parity"] = parity

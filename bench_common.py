@@ -218,7 +218,7 @@ def compact_line(out: dict, detail_path: str | None = None) -> dict:
             line["loop_closure_rccl"]["same_as_one_device"] = lc["verify"].get("same_as_one_device")
         if isinstance(line["loop_closure_rccl"].get("error"), str):
             line["loop_closure_rccl"]["error"] = line["loop_closure_rccl"]["error"][-600:]
-    for k in ("world", "build", "rank_units"):
+    for k in ("full", "world", "build", "rank_units"):
         if k in out:
             line[k] = out[k]
     if detail_path:

@@ -127,6 +127,40 @@ def test_compact_line_of_the_r05_result():
     assert "kernels" not in line and "kernels_timed_region" not in line and "kernels" not in b
 
 
+def test_dump_outputs_files_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: scores / poses / covs of the last timed step as float64
+    .npy files, unchanged; a batch over the byte budget is cut to the same
+    seeded rows of every array, identical from call to call."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+
+    rng = np.random.default_rng(5)
+    n = 37
+    final = (rng.normal(size=n), rng.normal(size=(n, 3)), rng.normal(size=(n, 9)))
+    d = tmp_path / "a"
+    bench.dump_outputs(str(d), final, 0, 1)
+    assert sorted(os.listdir(d)) == ["covs.npy", "poses.npy", "scores.npy"]
+    for name, a in zip(("scores", "poses", "covs"), final):
+        got = np.load(d / f"{name}.npy")
+        assert got.dtype == np.float64 and got.shape == a.shape and np.array_equal(got, a)
+    bench.dump_outputs(str(d), final, 1, 2)
+    assert np.array_equal(np.load(d / "poses_rank1.npy"), final[1])
+    # a budget of 10 scans' bytes: 10 rows, the same ones in every array and on every call
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 10 * 13 * 8)
+    e, f = tmp_path / "b", tmp_path / "c"
+    bench.dump_outputs(str(e), final, 0, 1)
+    bench.dump_outputs(str(f), final, 0, 1)
+    s, p, c = (np.load(e / f"{k}.npy") for k in ("scores", "poses", "covs"))
+    assert s.shape == (10,) and p.shape == (10, 3) and c.shape == (10, 9)
+    rows = [int(np.flatnonzero(final[0] == v)[0]) for v in s]
+    assert rows == sorted(set(rows))
+    assert np.array_equal(p, final[1][rows]) and np.array_equal(c, final[2][rows])
+    assert all(np.array_equal(np.load(e / k), np.load(f / k)) for k in os.listdir(e))
+    assert sum(os.path.getsize(e / k) for k in os.listdir(e)) <= 10 * 13 * 8 + 3 * 128
+
+
 def test_bench_plumbing_last_line_size_and_side_file(tmp_path):
     """The plumbing mode runs the config-2 emit path: the last stdout line is
     the compact one (under the budget, headline keys), the per-kernel tables

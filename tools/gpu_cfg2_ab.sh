@@ -2,13 +2,14 @@
 # Prints scorings/s, ms per step, the kernel share of the step and the host's
 # per-phase waits / work (host:* entries of the bench's kernel stats, per step).
 set -o pipefail
-mkdir -p gpurun_out
+O=${OUT:-out}
+mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 for cfg in "$@"; do
-  env $cfg timeout -k 10 300 python bench.py --no-cpu --no-latency --no-b109 > gpurun_out/cfg2ab.json 2> gpurun_out/cfg2ab.err || exit $?
+  env $cfg timeout -k 10 300 python bench.py --full --no-cpu --no-latency --no-b109 --detail-json "$O"/cfg2ab_detail.json > "$O"/cfg2ab.json 2> "$O"/cfg2ab.err || exit $?
   python3 -c "
 import json
-d = json.load(open('gpurun_out/bench_detail.json'))  # the whole result (the last stdout line is the compact one)
+d = json.load(open('$O/cfg2ab_detail.json'))  # the whole result (the last stdout line is the compact one)
 print('[$cfg]', round(d['value'] / 1e9, 3), 'G', round(d['ms_per_step'], 3), 'ms share', round(d['kernel_share_of_step'], 3))
 steps = d['steps']
 for k in d['kernels']:

@@ -19,7 +19,7 @@ tests)
   head -c 120 $O/stress_ties.json; echo ;;
 pmc)
   bash tools/pmc_roofline.sh $O/pmcr || exit $?
-  bash tools/pmc_roofline.sh $O/pmcb --levels sim --steps 2 --warmup 1 --no-cpu --no-latency --no-lc-leg \
+  bash tools/pmc_roofline.sh $O/pmcb --full --levels sim --steps 2 --warmup 1 --no-cpu --no-latency --no-lc-leg \
     --no-host-inputs || exit $?
   bash tools/pmc_roofline.sh $O/pmclc --workload loop_closure --steps 2 --warmup 1 --no-cpu || exit $?
   bash tools/pmc_roofline.sh $O/pmcw --workload willow --steps 2 --warmup 1 --no-cpu || exit $?
@@ -53,7 +53,7 @@ json.dump(a, open(f'{o}/counters_lc.json', 'w'), indent=1)
 PY
   cp $O/pmcr/counters.json $O/counters.json; echo "pmc done" ;;
 bench)
-  timeout -k 10 600 python bench.py > $O/bench_config2.json 2> $O/bench_config2.err || exit $?
+  timeout -k 10 600 python bench.py --full > $O/bench_config2.json 2> $O/bench_config2.err || exit $?
   timeout -k 10 300 python bench.py --workload loop_closure --steps 10 --warmup 2 > $O/bench_config3_loop_closure.json 2> $O/lc.err || exit $?
   timeout -k 10 300 python bench.py --workload willow --steps 20 --warmup 3 > $O/bench_config4_willow.json 2> $O/willow.err || exit $?
   timeout -k 10 300 python bench.py --workload willow --whole-map --steps 5 --warmup 1 --cpu-seconds 8 --counters-json profiles/$R/counters_willow_whole.json > $O/bench_config4_willow_whole.json 2> $O/willow_whole.err || exit $?
@@ -66,8 +66,8 @@ bench)
   rm -rf $O/prof_config2 $O/prof_b109 $O/prof_online
   # whole level-parts per dispatch (CSM_FIRST_WINDOWS=0): the summary's
   # per-dispatch averages are then the bench line's per-launch times
-  CSM_FIRST_WINDOWS=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_config2 -o run --output-format csv -- python3 bench.py --no-cpu --no-latency --no-b109 --no-lc-leg --no-host-inputs > $O/prof_config2.json 2> $O/prof_config2.err || exit $?
-  CSM_FIRST_WINDOWS=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_b109 -o run --output-format csv -- python3 bench.py --levels sim --no-cpu --no-latency --no-lc-leg --no-host-inputs > $O/prof_b109.json 2> $O/prof_b109.err || exit $?
+  CSM_FIRST_WINDOWS=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_config2 -o run --output-format csv -- python3 bench.py --full --no-cpu --no-latency --no-b109 --no-lc-leg --no-host-inputs > $O/prof_config2.json 2> $O/prof_config2.err || exit $?
+  CSM_FIRST_WINDOWS=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_b109 -o run --output-format csv -- python3 bench.py --full --levels sim --no-cpu --no-latency --no-lc-leg --no-host-inputs > $O/prof_b109.json 2> $O/prof_b109.err || exit $?
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_online -o run --output-format csv -- python3 bench.py --workload online --steps 200 --warmup 20 --no-cpu > $O/prof_online.json 2> $O/prof_online.err || exit $?
   echo "bench done" ;;
 pmcbench)

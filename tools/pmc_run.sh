@@ -5,7 +5,7 @@ set -e
 OUT=${1:-gpurun_out/pmc}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-B="python3 bench.py --steps 2 --warmup 1 --no-cpu --no-latency"
+B="python3 bench.py --full --steps 2 --warmup 1 --no-cpu --no-latency"
 timeout -k 10 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -- $B > "$OUT/fetch.json" 2> "$OUT/fetch.err"
 timeout -k 10 240 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -- $B > "$OUT/write.json" 2> "$OUT/write.err"
 python3 tools/pmc_traffic.py "$OUT/traffic.json" "$OUT/fetch" "$OUT/write" > "$OUT/traffic.txt"
