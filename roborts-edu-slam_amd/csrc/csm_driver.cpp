@@ -44,6 +44,14 @@ struct LevelRun {
   int64_t sw_stride = 0;
   int int_bad = 0;
   bool int_known = false;
+  // The level summed up for its launches (csm_level_decision.hpp): beam and
+  // point counts from level_prepare (they follow from the scans' sizes alone),
+  // the fixed-point range from the plan pass once every window is planned
+  // (int_known), or before any is when the level goes out in spans
+  // (range_preset: level_range_from_poses, handoff_in_range). Every call of
+  // the level carries it (WinSpan::level), so all decide alike.
+  LevelSummary shape;
+  bool range_preset = false;
   // the rows' cos/sin are left to the launch (csm_trig.hip): a device finish
   // (the host finish reads them), not the few-window path (its own copy)
   bool dev_trig = false;
@@ -75,6 +83,8 @@ struct LevelRun {
     sw_stride = 0;
     int_bad = 0;
     int_known = false;
+    shape = LevelSummary{};
+    range_preset = false;
     dev_trig = false;
     trig_bad = 0;
   }
@@ -128,6 +138,8 @@ int level_prepare(csm_ctx* c, int32_t n_scans, const int64_t* offsets, const csm
   if (st != CSM_OK) return c->fail(st, "invalid search window parameters");
   R.scan_of.reserve((size_t)n_scans);
   const bool ready = map_ready(c);
+  R.shape = LevelSummary{};
+  R.range_preset = false;
   int last_n = -1;  // the beam rule's verdict for the last point count (scans mostly share one)
   for (int k = 0; k < n_scans; ++k) {
     const int s = R.order ? R.order[k] : k;
@@ -142,10 +154,13 @@ int level_prepare(csm_ctx* c, int32_t n_scans, const int64_t* offsets, const csm
       if (!beam_rule(n, P.use_point_size, step, use, n_used))
         return c->fail(CSM_ERR_INVALID_ARG, "use_point_size <= 1 with n_points >= 2*use_point_size");
       last_n = n;
+      // the level's beam and point maxima: a count already seen changes neither
+      level_summary_add(R.shape, n, step, n_used, true);
     }
     R.scan_of.push_back(s);
     if (scan_grid) R.grid.push_back(scan_grid[s]);
   }
+  R.shape.n_windows = (int32_t)R.scan_of.size();  // (level_summary_add counted the distinct sizes)
   return CSM_OK;
 }
 
@@ -157,12 +172,19 @@ bool level_device_finish(const csm_ctx* c, const Dims& D, int nw) {
 }
 
 // Room for the level's plans and angle rows (pinned: uploaded by DMA).
-// spans: the level goes out in spans, so its launches read window plans not
-// planned yet (zeroed, as the kernel choice expects); otherwise every plan is
+// spans: the level goes out in spans, so its launches see window plans not
+// planned yet: zeroed, for the traffic they account (beams summed over the
+// level); no decision reads them (LevelRun::shape). Otherwise every plan is
 // written before the launch and the old ones are only resized (value-initialising
 // 2048 plans cost ~20 us of the serial chain, r06).
 int level_alloc(csm_ctx* c, const int64_t* offsets, LevelRun& R, HostBuf& rows, bool spans) {
   const int nw = (int)R.scan_of.size();
+  // the grid's fixed-point copy, whose pitch and value bound the plan pass's
+  // range check reads (level_plan_one): before this, the first level after a
+  // new grid was checked against the previous grid's (a fresh context: zeros,
+  // which pass every window)
+  int gst = ensure_int_grid(c);
+  if (gst != CSM_OK) return gst;
   if (spans)
     R.plans.assign((size_t)nw, WindowPlan{});
   else
@@ -218,7 +240,20 @@ int level_launch(csm_ctx* c, LevelRun& R, WinSpan sp = WinSpan{}) {
   R.dev = level_device_finish(c, D, nw);
   sp.sw_ready = R.sw;
   sp.sw_stride = R.sw_stride;
-  sp.int_all = R.int_known && !__atomic_load_n(&R.int_bad, __ATOMIC_RELAXED);
+  // the level's fixed-point range: what the plan pass found once every window
+  // is planned, or what was settled before the first span (range_preset: every
+  // window in range, or the level would not go out in spans). A window the
+  // plan then finds out of range after all contradicts the bound it was
+  // launched under: an error, never a span scored by other kernels.
+  const bool int_bad = __atomic_load_n(&R.int_bad, __ATOMIC_RELAXED) != 0;
+  if (R.range_preset) {
+    if (c->int_ok && int_bad)
+      return c->fail(CSM_ERR_INVALID_ARG, "a window left the fixed-point range its level was launched for");
+  } else {
+    if (!R.int_known) return c->fail(CSM_ERR_INVALID_ARG, "level launched in spans without its range settled");
+    R.shape.in_range = !int_bad;
+  }
+  sp.level = &R.shape;
   sp.dev_trig = R.dev_trig;
   sp.rows_gen = R.dev_trig && !__atomic_load_n(&R.trig_bad, __ATOMIC_RELAXED);
   const int st = run_windows(c, R.P, D, G, R.plans, R.pt_off, R.angles, (size_t)nw * (size_t)D.n_angles, R.grid,
@@ -256,6 +291,51 @@ int level_begin(csm_ctx* c, int32_t n_scans, const int64_t* offsets, const csm_p
   return CSM_OK;
 }
 
+// Every window of a prepared level inside the fixed-point range, from the
+// scans' poses alone, before any window is planned: what level_plan_one will
+// find (the same x0, y0 as plan_window_into, the same check; level_in_range
+// tries the windows' two extreme corners before going window by window).
+RangeEnv range_env(const csm_ctx* c) { return RangeEnv{c->pts_maxabs, c->pitch, c->int_max_abs, c->int_exp}; }
+
+bool level_range_from_poses(const csm_ctx* c, const LevelRun& R, const Geometry& G, const int64_t* offsets,
+                            const double* poses) {
+  const double half = (R.P.search_space_size / G.mres) * 0.5;
+  const double far = (double)(R.D.n_space - 1) * (R.P.search_space_resolution / G.mres);
+  int last_n = -1, last_used = 0;  // (level_prepare accepted every size)
+  auto start = [&](int i, double& x0, double& y0, int& n_used) {
+    const int s = R.scan_of[(size_t)i];
+    double m[3];
+    G.to_map(poses + 3 * (size_t)s, m);
+    x0 = m[0] - half;
+    y0 = m[1] - half;
+    const int n = (int)(offsets[s + 1] - offsets[s]);
+    if (n != last_n) {
+      int step, use;
+      (void)beam_rule(n, R.P.use_point_size, step, use, last_used);
+      last_n = n;
+    }
+    n_used = last_used;
+  };
+  return level_in_range((int)R.scan_of.size(), start, far, range_env(c));
+}
+
+// The same for the level N a split hand-off launches while the second half
+// of the previous level R is still being completed: N's windows bounded from
+// R's (handoff_reach_bound over the hull of R's windows and centres) at N's
+// most beams. False when the bound does not clear the range: the hand-off
+// then launches N once, after every window is planned.
+bool handoff_in_range(const csm_ctx* c, const LevelRun& R, const LevelRun& N, const Geometry& G) {
+  const double pfar = (double)(R.D.n_space - 1) * (R.P.search_space_resolution / G.mres);
+  const double half = (N.P.search_space_size / G.mres) * 0.5;
+  const double far = (double)(N.D.n_space - 1) * (N.P.search_space_resolution / G.mres);
+  Hull X, Y;
+  for (const WindowPlan& W : R.plans) {
+    X.add(W.x0, W.center[0], pfar);
+    Y.add(W.y0, W.center[1], pfar);
+  }
+  return range_env(c).ok(handoff_reach_bound(X, Y, half, far), N.shape.max_n_used);
+}
+
 // level_begin with the plan in growing pieces: the pool plans the first
 // `first` windows and their scoring goes out at once, then the next
 // span_growth times as many while those score, and so on; the finish follows
@@ -271,16 +351,26 @@ int level_begin_split(csm_ctx* c, int32_t n_scans, const int64_t* offsets, const
   if (st != CSM_OK) return st;
   if (c->profiling) c->account("host:first:prepare", (float)(now_ms() - t_in), 0.0, 0.0);
   const int nw = (int)R.scan_of.size();
-  if (first <= 0 || nw < 2 * first || !level_device_finish(c, R.D, nw))
-    return level_begin(c, n_scans, offsets, P, poses, responses, nullptr, R, scan_grid, skip_lists);
+  // In spans only with the level's one decision settled before the first of
+  // them (LevelRun::shape): the beam and point maxima are level_prepare's, and
+  // every window must be in fixed-point range by its scan's pose; a level with
+  // a window out of range goes out in one launch (fp64 columns for all of it).
+  bool spans = first > 0 && nw >= 2 * first && level_device_finish(c, R.D, nw);
+  const Geometry G(c->info);
+  if (spans) {
+    if ((st = ensure_int_grid(c)) != CSM_OK) return st;
+    spans = !c->int_ok || level_range_from_poses(c, R, G, offsets, poses);
+  }
+  if (!spans) return level_begin(c, n_scans, offsets, P, poses, responses, nullptr, R, scan_grid, skip_lists);
   const double t0 = now_ms();
   if ((st = level_alloc(c, offsets, R, c->h_angles, true)) != CSM_OK) return st;
-  const Geometry G(c->info);
+  R.shape.in_range = true;
+  R.range_preset = true;
   if (c->profiling) c->account("host:first:prepare+alloc", (float)(now_ms() - t_in), 0.0, 0.0);
   int w0 = 0;
   for (int64_t sz = first; w0 < nw; sz *= std::max(2, c->span_growth)) {
     // the last span takes the rest when it would leave less than a span behind
-    const int w1 = (nw - w0 <= 2 * sz) ? nw : w0 + (int)sz;
+    const int w1 = level_span_end(nw, w0, sz);
     const double tp = now_ms();
     c->parallel_for(w1 - w0, c->host_threads, [&](int i) { level_plan_one(c, R, G, offsets, poses, w0 + i); });
     R.int_known = w1 == nw;
@@ -446,9 +536,17 @@ int level_end_begin(csm_ctx* c, LevelRun& R, LevelRun& N, int32_t n_scans, const
   if ((st = early ? level_wait_fast(c, R) : level_join(c, R)) != CSM_OK) return st;
   const double t2 = now_ms();
   std::swap(c->h_angles, c->h_angles_next);
-  split = split && early && nw >= c->split_handoff_min && level_device_finish(c, N.D, nw);
-  if ((st = level_alloc(c, offsets, N, c->h_angles, split)) != CSM_OK) return st;
   const Geometry G(c->info);
+  // (in two spans only when N's one decision is settled before its first: its
+  // maxima are level_prepare's, its windows are bounded in fixed-point range
+  // from R's; otherwise one launch after completion)
+  split = split && early && nw >= c->split_handoff_min && level_device_finish(c, N.D, nw) &&
+          (!c->int_ok || handoff_in_range(c, R, N, G));
+  if ((st = level_alloc(c, offsets, N, c->h_angles, split)) != CSM_OK) return st;
+  if (split) {
+    N.shape.in_range = true;
+    N.range_preset = true;
+  }
   const int threads = (nw >= 64) ? c->host_threads : 1;
   auto one = [&](int i, bool defer) {
     if (!level_complete_one(R, G, poses, covs, responses, nullptr, i, defer)) return false;
@@ -568,6 +666,9 @@ int with_slot(csm_ctx* c, const PipeJob& J, int h, F&& f) {
 // -> 0.613 ms, the phase kernel 0.252 -> 0.245; ranks in contiguous eighths
 // (each XCD one region of the map) made the pair kernel 0.848 ms, the XCDs'
 // regions holding unequal work. Scans are independent: no result changes.
+// (tests/test_gpu_mixed_batches.py restates this order and job_setup's split
+// in Python, _window_order and _parts, to place scans of chosen lengths in
+// chosen spans: keep them in step.)
 #ifndef CSM_WINDOW_ORDER  // 0: scan order (A/B builds)
 #define CSM_WINDOW_ORDER 1
 #endif

@@ -25,6 +25,7 @@
 #include "csm_gridmap_internal.hpp"
 #include "host_math.hpp"
 #include "csm_pyramid.hpp"
+#include "csm_level_decision.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -736,11 +737,15 @@ struct WinSpan {
   int w0 = 0, w1 = -1;  // w1 < 0: every window
   bool score = true, finish = true;
   // the caller's plan pass filled the windows' ScanWork into the slot's
-  // staging (c->h_sw, this pointer) at sw_stride, and found every window of
-  // the level in fixed-point range (int_all): run_windows skips both loops
+  // staging (c->h_sw, this pointer) at sw_stride: run_windows skips that loop
   const ScanWork* sw_ready = nullptr;
   int64_t sw_stride = 0;
-  bool int_all = false;
+  // the level's summary (csm_level_decision.hpp), made from every window of
+  // the level before its first call: every call of the level decides its
+  // kernels and its finish from it. Required for a part of a level (whose
+  // later windows may not be planned yet); a whole-level call without it sums
+  // up its plans itself.
+  const LevelSummary* level = nullptr;
   // the plan left the rows' cos/sin to the device (plan_window_into host_trig
   // false): the launch computes them after the rows' copy (csm_trig.hip)
   bool dev_trig = false;

@@ -205,12 +205,8 @@ bool phase_table(double f, int ns, int margin_log2, csm::PhaseTable& T) {
 // wrap (every endpoint within 2^30 bytes of a row); the context's grid must
 // be eligible too (c->int_ok).
 bool int_mode_window_ok(const csm_ctx* c, const Dims& D, double f, const WindowPlan& W) {
-  const double far = (double)(D.n_space - 1) * f;
-  const double span = std::max(std::max(std::fabs(W.x0), std::fabs(W.x0 + far)),
-                               std::max(std::fabs(W.y0), std::fabs(W.y0 + far)));
-  const double R = c->pts_maxabs * (1.0 + 1e-9) + span + 2.0;
-  if (!(R * 4.0 * (double)c->pitch < std::ldexp(1.0, 30))) return false;
-  return !((double)W.n_used * c->int_max_abs * std::ldexp(1.0, c->int_exp) > std::ldexp(1.0, 53));
+  return fixed_point_range_ok(window_reach(W.x0, W.y0, (double)(D.n_space - 1) * f), c->pts_maxabs, c->pitch, W.n_used,
+                              c->int_max_abs, c->int_exp);
 }
 
 // ... for windows [i0, i1)
@@ -443,10 +439,7 @@ int run_windows_small(csm_ctx* c, const csm_param& P, const Dims& D, const Geome
 #define CSM_TAIL_FINISH 1
 #endif
 constexpr bool kTailFinish = CSM_TAIL_FINISH != 0;
-#ifndef CSM_TAIL_MAX_BEAMS
-#define CSM_TAIL_MAX_BEAMS 512
-#endif
-constexpr int kTailMaxBeams = CSM_TAIL_MAX_BEAMS;  // levels summing more beams keep the separate fast pass
+// (kTailMaxBeams, above which a level keeps the separate fast pass: csm_level_decision.hpp)
 
 int run_windows(csm_ctx* c, const csm_param& P, const Dims& D, const Geometry& G,
                 const std::vector<WindowPlan>& plans, const std::vector<int64_t>& pt_offsets,
@@ -467,8 +460,9 @@ int run_windows(csm_ctx* c, const csm_param& P, const Dims& D, const Geometry& G
   const double tp1 = c->profiling ? now_ms() : 0.0;  // (the deferred event reads are profiling's own cost)
   if (c->profiling) c->account("host:launch:flush_events", (float)(tp1 - tp0), 0.0, 0.0);
   if (!whole) {
+    // (a part of a level cannot sum the level up itself: later windows' plans may not be written yet)
     bool ok = mode == Finish::kDevice && (sp.score || sp.finish) && 0 <= w0 && w0 < w1 && w1 <= nw &&
-              n_angle_entries == (size_t)nw * (size_t)D.n_angles;
+              n_angle_entries == (size_t)nw * (size_t)D.n_angles && sp.level;
     for (int w = w0; ok && w < w1; ++w) ok = plans[(size_t)w].angle_off == (int64_t)w * D.n_angles;
     if (!ok) return c->fail(CSM_ERR_INVALID_ARG, "run_windows: bad window span");
   }
@@ -481,8 +475,21 @@ int run_windows(csm_ctx* c, const csm_param& P, const Dims& D, const Geometry& G
   const int64_t col_blocks = (n_cols + 63) / 64;
   if (n_cols >= INT32_MAX) return c->fail(CSM_ERR_UNSUPPORTED, "window too large for one launch");
   const double f = P.search_space_resolution / G.mres;
-  // (sp.int_all: the plan pass found every window of the level in range)
-  const bool use_int = (sp.int_all && c->int_ok) || int_mode_ok(c, D, f, plans, (size_t)w0, (size_t)w1);
+  // The level summed up (csm_level_decision.hpp): the driver's, made from
+  // every window of the level before its first call, or this whole-level
+  // call's own plans. Everything below that depends on the windows (fixed
+  // point or fp64, the kernel family, its short forms, the fused finish) is
+  // decided from it and never from this call's span, so every call of a level
+  // decides alike.
+  LevelSummary S;
+  if (sp.level) {
+    S = *sp.level;
+    if (S.n_windows != nw) return c->fail(CSM_ERR_INVALID_ARG, "run_windows: the level's summary is of other windows");
+  } else {
+    for (const WindowPlan& W : plans) level_summary_add(S, W.n_points, W.step, W.n_used, true);
+    S.in_range = int_mode_ok(c, D, f, plans);
+  }
+  const bool use_int = c->int_ok && S.in_range;
   if (whole && mode != Finish::kBest && use_int && small_launch(c, D, nw))
     return run_windows_small(c, P, D, G, plans, pt_offsets, angles, n_angle_entries, grid_index,
                              mode == Finish::kDevice, pend, skip_lists);
@@ -496,19 +503,28 @@ int run_windows(csm_ctx* c, const csm_param& P, const Dims& D, const Geometry& G
     rows_sq = csm::rows_pick_sq(D.n_space, (int)std::floor(span * (1.0 + 1e-9) + 1e-9) + 2);
     if (c->info.size_x < 4 * rows_sq) rows_sq = 0;
   }
-  // the box kernels' beam offsets are 24-bit products (BoxWave::point: the
-  // point index and step * 16 each under 2^24). Over every window of the level,
-  // not this call's span: the fused-finish decision below depends on it and must
-  // be the same in every call of a level (level_ctr counts all of its windows).
-  bool box_points_ok = true;
-  for (const WindowPlan& W : plans) {
-    box_points_ok = W.n_points < (1 << 24) && (int64_t)W.step * 16 < (1 << 24);
-    if (!box_points_ok) break;
-  }
+  // The kernel families the level's window shape and step admit (LevelCaps),
+  // then the decision (level_decide): the same in every call of the level.
   // v6 box kernel: whole-cell window step (use_int bounds |t| < 2^24 cells,
-  // which its rounding margin needs)
-  const bool box = use_int && box_points_ok && c->box_kernel && f == 1.0 && csm::box_supported(D.n_space) &&
-                   c->pitch >= c->info.size_x + csm::kGridiPadCols;
+  // which its rounding margin needs), beam offsets that are 24-bit products
+  // (LevelSummary::points_ok).
+  // v7 phase kernel: sub-cell window step with an instantiated bucket shape.
+  // v8 tiny-window kernel: a sub-cell step whose whole span is under one cell.
+  const bool sig = signalled_finish(c, mode);
+  const bool pad_ok = c->pitch >= c->info.size_x + csm::kGridiPadCols;
+  csm::PhaseTable PT{};
+  LevelCaps K;
+  K.int_grid = c->int_ok;
+  K.tail_finish = kTailFinish && sig;
+  K.box = c->box_kernel && f == 1.0 && csm::box_supported(D.n_space) && pad_ok;
+  K.phase = use_int && c->phase_kernel && f < 1.0 && phase_table(f, D.n_space, c->phase_margin_log2, PT) &&
+            csm::phase_supported(D.n_space, PT.cells, PT.nq) && pad_ok;
+  K.tiny = c->tiny_kernel && f < 1.0 && csm::tiny_supported(D.n_space, f) && pad_ok &&
+           (int64_t)c->pitch * (c->info.size_y + csm::kGridiPadRows) * 4 < INT32_MAX;
+  const LevelDecision dec = level_decide(S, K, w0, w1);
+  if (!dec.valid) return c->fail(CSM_ERR_INVALID_ARG, "run_windows: bad window span");
+  const bool box_points_ok = dec.box_points_ok;
+  const bool box = dec.box;
   if (box) rows_sq = 0;
   // v11: the box read through the grid's palette (one byte per cell), pairs
   // of equal-count runs over the strip copies (palettes of <= 16 values);
@@ -526,19 +542,11 @@ int run_windows(csm_ctx* c, const csm_param& P, const Dims& D, const Geometry& G
                          c->pitch >= c->info.size_x + csm::kGridiPadCols &&
                          (int64_t)nw * tile_n * tile_n * D.n_angles <= INT32_MAX;
   if (box_tiled) rows_sq = 0;
-  // v7 phase kernel: sub-cell window step with an instantiated bucket shape
-  csm::PhaseTable PT{};
-  const bool phase = !box && use_int && c->phase_kernel && f < 1.0 &&
-                     phase_table(f, D.n_space, c->phase_margin_log2, PT) &&
-                     csm::phase_supported(D.n_space, PT.cells, PT.nq) &&
-                     c->pitch >= c->info.size_x + csm::kGridiPadCols;
+  const bool phase = dec.phase;
   if (phase) rows_sq = 0;
   if (phase && c->phase_strips && (st = ensure_istrips(c)) != CSM_OK) return st;
   const bool phase_st = phase && c->phase_strips && c->istrips_ok;
-  // v8 tiny-window kernel: a sub-cell step whose whole span is under one cell
-  const bool tiny = !box && !phase && use_int && c->tiny_kernel && f < 1.0 && csm::tiny_supported(D.n_space, f) &&
-                    c->pitch >= c->info.size_x + csm::kGridiPadCols &&
-                    (int64_t)c->pitch * (c->info.size_y + csm::kGridiPadRows) * 4 < INT32_MAX;
+  const bool tiny = dec.tiny;
   if (tiny) rows_sq = 0;
   const int64_t rows_groups = rows_sq ? 64 / D.n_space : 1;
   const int64_t bps = box_tiled ? (int64_t)tile_n * tile_n * D.n_angles
@@ -552,25 +560,30 @@ int run_windows(csm_ctx* c, const csm_param& P, const Dims& D, const Geometry& G
   ScanWork* sw = (ScanWork*)c->h_sw.p;  // pinned staging
   // Host-signal finish (the device finish with its fast pass): FinishOut goes
   // straight to coherent pinned memory and the pass that ends last sets a flag
-  // the host spins on; the scoring kernel clears the flagged-window count.
-  const bool sig = signalled_finish(c, mode);
+  // the host spins on; the scoring kernel clears the flagged-window count
+  // (sig, above).
   // The fused fast finish (csm_tail.hpp): the level's scoring launches finish
-  // their windows themselves, no fast-pass launch. The same decision in every
-  // call of a level (its spans and its finish-only call): every window in
-  // fixed-point range and a kernel that carries the finish. Each window's
-  // scores then start on a 128-byte line of their own (no line is shared by
-  // two windows: a finisher's sc1 loads never find a line another window's
-  // finisher brought into its L2 before that window's scores were stored).
+  // their windows themselves, no fast-pass launch: every window in
+  // fixed-point range, a kernel that carries the finish, and no window
+  // summing more than kTailMaxBeams beams. The decision is level_decide's,
+  // from the summary of the whole level, so a level's spans and its
+  // finish-only call all reach it whatever windows each of them holds and
+  // whichever of the level's plans were written when it was made (until r06
+  // each call took the maxima over the plans written so far, zeros elsewhere:
+  // a first span of short scans fused its finish, and the later calls of a
+  // level with a longer scan ran the separate fast pass over every window,
+  // the first span's a second time, with level_ctr left part-counted). Each
+  // window's scores then start on a 128-byte line of their own (no line is
+  // shared by two windows: a finisher's sc1 loads never find a line another
+  // window's finisher brought into its L2 before that window's scores were
+  // stored).
   // Only for short scoring waves: each wave waits for its write-through score
   // stores before counting in, which at B = 1081 costs the scoring launches
   // as much as the separate fast pass costs (r05: +55 / +30 / +43 us on the
   // box / phase / tiny launches against -32 / -31 / -29 us of fast passes);
   // at B = 109 the host gets each level's signal ~50 us earlier and the step
   // shortens.
-  int max_beams = 0;
-  for (const WindowPlan& W : plans) max_beams = std::max(max_beams, (int)W.n_used);
-  const bool tail = kTailFinish && sig && (box || phase || tiny) && max_beams <= kTailMaxBeams &&
-                    (whole ? use_int : (sp.int_all && c->int_ok) || int_mode_ok(c, D, f, plans, 0, (size_t)nw));
+  const bool tail = dec.tail;
   const int64_t stride = score_stride(c, D, mode);
   // the plan pass may have filled this call's ScanWork already (WinSpan::sw_ready:
   // level_plan_one, into this slot's staging, at this stride)
@@ -578,7 +591,10 @@ int run_windows(csm_ctx* c, const csm_param& P, const Dims& D, const Geometry& G
     fill_scan_work(D, plans, pt_offsets, grid_index, sw, (size_t)w0, (size_t)w1, stride);
   LevelWork L = make_level_work(c, P, D, G, nr, use_int);
   L.blocks_per_scan = box_tiled ? D.n_angles : (int32_t)bps;  // per (window, tile) when tiled
-  L.max_n_used = max_beams;
+  // level-wide, not this span's: the pair and phase kernels' short forms hold
+  // for any window of at most that many beams, and one form per level keeps a
+  // level's spans on one kernel instantiation
+  L.max_n_used = dec.max_n_used;
   L.tile_n = box_tiled ? tile_n : 0;
   if (box_pair) {
     L.pal_n = c->pal_n;
@@ -963,6 +979,11 @@ int run_windows(csm_ctx* c, const csm_param& P, const Dims& D, const Geometry& G
   p.defer_timing = sig;
   if ((e = hipEventRecord(c->ev_done, done_stream)) != hipSuccess) return c->hip_fail(e, "hipEventRecord");
   if (c->profiling && tl2 > 0.0) c->account("host:launch:finish", (float)(now_ms() - tl2), 0.0, 0.0);
+  if (c->profiling && sig && mode == Finish::kDevice) {  // how the level's fast finish ran (launches: levels; scorings: windows)
+    char nm[48];
+    std::snprintf(nm, sizeof(nm), "finish:%s<%lld>", tail ? "fused" : "separate", (long long)D.n_cand);
+    c->account(nm, 0.f, 0.0, (double)nw);
+  }
   if (pend) return CSM_OK;
   return wait_run(c, p);
 }
