@@ -403,6 +403,7 @@ struct csm_ctx {
   // the host's libm passed libm_sincos_table()'s checks
   bool device_trig = true;
   csmh::DevBuf trig_tab;      // libm's sincos table on this device (uploaded on first use)
+  bool trig_tab_ready = false;  // ... its copy was enqueued and its stream drained (ensure_trig_table)
   std::unique_ptr<csmh::ThreadPool> pool;
   template <class F>
   void parallel_for(int n, int threads, F&& fn) {
@@ -758,6 +759,9 @@ struct WinSpan {
 // found or the restated sincos did not equal ::sincos on the check's
 // arguments (csm_launch.cpp; libm_sincos_table.hpp). Located once.
 const double* libm_sincos_table();
+// ... on the device (c->trig_tab), uploaded on `s` by the first call that gets
+// that far; CSM_ERR_UNSUPPORTED without the host table (csm_launch.cpp)
+int ensure_trig_table(csm_ctx* c, hipStream_t s);
 
 bool signalled_finish(const csm_ctx* c, Finish mode);
 int64_t score_stride(const csm_ctx* c, const Dims& D, Finish mode);

@@ -1,8 +1,9 @@
 // csm_launch.cpp — a level's windows on the device: the window plan (the
 // reference's angle LUT with host glibc sincos, AngleSearchLookUpTable
-// :150-186, and the search start :538-548), the choice of scoring kernel, the
-// launch with its device finish (run_windows, run_windows_small), the joins
-// and the per-launch HIP-event accounting.
+// :150-186, and the search start :538-548), the launch of a level's windows
+// with its device finish (run_windows: a sequence of steps over one Launch,
+// the kernel chosen once by launch_shape; run_windows_small), the joins and
+// the per-launch HIP-event accounting.
 #include "csm_host.hpp"
 #include "libm_sincos_table.hpp"
 
@@ -294,6 +295,84 @@ bool small_launch(const csm_ctx* c, const Dims& D, int nw) {
          D.n_cand * (int64_t)nw <= INT32_MAX && csm::finish_lds_bytes(D.n_cand) <= 160 * 1024;
 }
 
+// A fresh nonzero value of the context's sequence: a launch's flag value,
+// also the tag its scoring kernel puts on the list.
+int32_t draw_tag(csm_ctx* c) {
+  int32_t v = (int32_t)(++c->flag_seq & 0x7FFFFFFF);
+  if (v == 0) v = (int32_t)(++c->flag_seq & 0x7FFFFFFF);
+  return v;
+}
+
+// Device counters that start at zero and that every launch leaves at zero:
+// when the buffer holds fewer than `need` bytes it grows to `grow` and all of
+// it is zeroed on the context's stream. sync: the stream is drained first.
+int ensure_zeroed(csm_ctx* c, DevBuf& b, size_t need, size_t grow, bool sync, const char* what) {
+  if (need <= b.cap) return CSM_OK;
+  hipError_t e;
+  if ((sync && (e = hipStreamSynchronize(c->stream)) != hipSuccess) || (e = b.ensure(grow)) != hipSuccess ||
+      (e = hipMemsetAsync(b.p, 0, b.cap, c->stream)) != hipSuccess)
+    return c->hip_fail(e, what);
+  return CSM_OK;
+}
+
+// ... and the coherent host memory the finish writes into (at least 64 KiB)
+int ensure_host_zeroed(csm_ctx* c, HostBuf& b, size_t need, const char* what) {
+  if (need <= b.cap) return CSM_OK;
+  const hipError_t e = b.ensure(std::max<size_t>(need, 64 * 1024), hipHostMallocCoherent);
+  if (e != hipSuccess) return c->hip_fail(e, what);
+  std::memset(b.p, 0, b.cap);
+  return CSM_OK;
+}
+
+// The finish's arguments every mode shares; the lists, counters, flags and
+// FinishArgs::wide_windows are the caller's.
+csm::FinishArgs finish_args(const csm_param& P, const Dims& D, const Geometry& G, int skip_lists) {
+  csm::FinishArgs A{};
+  A.n_cand = D.n_cand;
+  A.n_space = D.n_space;
+  A.step_cells = P.search_space_resolution / G.mres;
+  A.lin_tol = P.search_space_resolution / G.mres;
+  A.skip_lists = skip_lists | own_lists_skip(P.type);
+  return A;
+}
+
+// What every launch's PendingRun holds: the names, the algorithmic traffic
+// (one fp32 grid read per summed beam per candidate) and the context's events.
+void pending_base(csm_ctx* c, const Dims& D, const std::vector<WindowPlan>& plans, const char* kname, PendingRun& p) {
+  p = PendingRun{};
+  std::snprintf(p.kname, sizeof(p.kname), "%s", kname);
+  std::snprintf(p.fname, sizeof(p.fname), "finish_kernel<%lld>", (long long)D.n_cand);
+  double beams = 0.0;
+  for (const WindowPlan& W : plans) beams += (double)W.n_used;
+  p.alg_bytes = beams * (double)D.n_cand * 4.0;
+  p.scorings = (double)plans.size() * (double)D.n_cand;
+  p.finish_bytes = (double)plans.size() * (double)D.n_cand * 8.0;
+  p.timed = c->profiling;
+  p.ev0 = c->ev0;
+  p.ev1 = c->ev1;
+  p.ev2 = c->ev2;
+  p.done = c->ev_done;
+}
+
+// libm's sincos table on the device, uploaded once per context on the stream
+// of the first call that needs it. Ready only once the copy was enqueued and
+// that stream drained (once, during warm-up): a later use from another stream
+// reads a finished table, and after a failed copy the next call uploads again
+// instead of launching against an empty table.
+int ensure_trig_table(csm_ctx* c, hipStream_t s) {
+  if (c->trig_tab_ready) return CSM_OK;
+  const double* tab = libm_sincos_table();
+  if (!tab) return c->fail(CSM_ERR_UNSUPPORTED, "device trig without the libm table");
+  const size_t bytes = csm::libm::kSincosTableDoubles * sizeof(double);
+  hipError_t e;
+  if ((e = c->trig_tab.ensure(bytes)) != hipSuccess) return c->hip_fail(e, "hipMalloc(sincos table)");
+  if ((e = hipMemcpyAsync(c->trig_tab.p, tab, bytes, hipMemcpyHostToDevice, s)) != hipSuccess ||
+      (e = hipStreamSynchronize(s)) != hipSuccess)
+    return c->hip_fail(e, "hipMemcpyAsync(sincos table)");
+  c->trig_tab_ready = true;
+  return CSM_OK;
+}
+
 // Few-window launch: the split kernel (csm_split.hip) scores, the fast and
 // exact finishes write each window's FinishOut straight into coherent pinned
 // host memory, and the exact pass stores a fresh flag value last (wait_run
@@ -305,6 +384,7 @@ int run_windows_small(csm_ctx* c, const csm_param& P, const Dims& D, const Geome
                       bool device_finish, PendingRun* pend, int skip_lists) {
   const int nw = (int)plans.size();
   hipError_t e;
+  int st;
   // device carve: done counter (fixed place: zero between launches) | scans |
   // angles | need | list
   const size_t o_done = 0, o_scans = 64;
@@ -312,28 +392,17 @@ int run_windows_small(csm_ctx* c, const csm_param& P, const Dims& D, const Geome
   const size_t o_need = (o_ang + n_angle_entries * sizeof(AngleEntry) + 15) & ~(size_t)15;
   const size_t o_list = (o_need + (size_t)nw * 4 + 7) & ~(size_t)7;  // {count, tag}: one 8-byte word
   const size_t dev_bytes = o_list + (size_t)(nw + 2) * 4;
-  if (dev_bytes > c->small_dev.cap) {
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hip_fail(e, "hipStreamSynchronize(small)");
-    if ((e = c->small_dev.ensure(dev_bytes * 2)) != hipSuccess) return c->hip_fail(e, "hipMalloc(small)");
-    if ((e = hipMemsetAsync(c->small_dev.p, 0, c->small_dev.cap, c->stream)) != hipSuccess)
-      return c->hip_fail(e, "hipMemsetAsync(small)");
-  }
+  if ((st = ensure_zeroed(c, c->small_dev, dev_bytes, dev_bytes * 2, true, "small launch buffer")) != CSM_OK) return st;
   char* dv = (char*)c->small_dev.p;
   ScanWork* d_scans = (ScanWork*)(dv + o_scans);
   AngleEntry* d_angles = (AngleEntry*)(dv + o_ang);
-  int32_t* d_need = (int32_t*)(dv + o_need);
   int32_t* d_list = (int32_t*)(dv + o_list);
-  int32_t* d_done = (int32_t*)(dv + o_done);
   // host side: the windows' staging (laid out as the device carve from
   // o_scans on), and FinishOut[nw] + the flag (coherent)
   const size_t in_bytes = o_ang - o_scans + n_angle_entries * sizeof(AngleEntry);
   const size_t out_flag = ((size_t)nw * sizeof(csm::FinishOut) + 63) & ~(size_t)63;
   if ((e = c->h_small_in.ensure(in_bytes)) != hipSuccess) return c->hip_fail(e, "hipHostMalloc(small in)");
-  if (out_flag + 64 > c->h_small_out.cap) {
-    if ((e = c->h_small_out.ensure(std::max<size_t>(out_flag + 64, 64 * 1024), hipHostMallocCoherent)) != hipSuccess)
-      return c->hip_fail(e, "hipHostMalloc(small out)");
-    std::memset(c->h_small_out.p, 0, c->h_small_out.cap);
-  }
+  if ((st = ensure_host_zeroed(c, c->h_small_out, out_flag + 64, "hipHostMalloc(small out)")) != CSM_OK) return st;
   csm::FinishOut* h_out = (csm::FinishOut*)c->h_small_out.p;
   int32_t* h_flag = (int32_t*)((char*)c->h_small_out.p + out_flag);
   ScanWork* sw = (ScanWork*)c->h_small_in.p;
@@ -351,21 +420,15 @@ int run_windows_small(csm_ctx* c, const csm_param& P, const Dims& D, const Geome
   const size_t slab_bytes = (size_t)nw * (size_t)chunks * (size_t)splits * csm::kSplitThreads * sizeof(int32_t);
   const size_t arrive_bytes = (size_t)nw * (size_t)chunks * sizeof(int32_t);
   if ((e = c->split_slab.ensure(slab_bytes)) != hipSuccess) return c->hip_fail(e, "hipMalloc(split slab)");
-  if (arrive_bytes > c->split_arrive.cap) {  // counters start at zero; each launch leaves them at zero
-    if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hip_fail(e, "hipStreamSynchronize(split)");
-    if ((e = c->split_arrive.ensure(arrive_bytes * 2)) != hipSuccess) return c->hip_fail(e, "hipMalloc(split arrive)");
-    if ((e = hipMemsetAsync(c->split_arrive.p, 0, c->split_arrive.cap, c->stream)) != hipSuccess)
-      return c->hip_fail(e, "hipMemsetAsync(split arrive)");
-  }
+  if ((st = ensure_zeroed(c, c->split_arrive, arrive_bytes, arrive_bytes * 2, true, "split arrive counters")) != CSM_OK)
+    return st;
   csm::SplitWork W{};
   W.splits = splits;
   W.chunks = (int32_t)chunks;
   W.slab = (int32_t*)c->split_slab.p;
   W.arrive = (int32_t*)c->split_arrive.p;
   W.clear_word = d_list;
-  // the launch's flag value, also the tag its scoring kernel puts on the list
-  int32_t flag_value = (int32_t)(++c->flag_seq & 0x7FFFFFFF);
-  if (flag_value == 0) flag_value = (int32_t)(++c->flag_seq & 0x7FFFFFFF);
+  const int32_t flag_value = draw_tag(c);
   W.clear_tag = flag_value;
   W.inline_window = (nw == 1 && D.n_angles <= csm::kSplitArgAngles && n_angle_entries == (size_t)D.n_angles) ? 1 : 0;
   if (W.inline_window) {
@@ -388,49 +451,31 @@ int run_windows_small(csm_ctx* c, const csm_param& P, const Dims& D, const Geome
   if (c->profiling && (e = hipEventRecord(c->ev1, c->stream)) != hipSuccess) return c->hip_fail(e, "hipEventRecord");
   PendingRun local;
   PendingRun& p = pend ? *pend : local;
-  p = PendingRun{};
-  std::snprintf(p.kname, sizeof(p.kname), "score_split_kernel<%d,%d>", D.n_space, splits);
-  double beams = 0.0;
-  for (const WindowPlan& Wp : plans) beams += (double)Wp.n_used;
-  p.alg_bytes = beams * (double)D.n_cand * 4.0;
-  p.scorings = (double)nw * (double)D.n_cand;
-  p.timed = c->profiling;
-  p.ev0 = c->ev0;
-  p.ev1 = c->ev1;
-  p.ev2 = c->ev2;
-  p.done = c->ev_done;
+  char kname[48];
+  std::snprintf(kname, sizeof(kname), "score_split_kernel<%d,%d>", D.n_space, splits);
+  pending_base(c, D, plans, kname, p);
   if (!device_finish) {  // every score to the host (csm_score_window, host std::sort)
     if ((e = c->h_scores.ensure(bytes)) != hipSuccess) return c->hip_fail(e, "hipHostMalloc(scores)");
     if ((e = hipMemcpyAsync(c->h_scores.p, c->scores.p, bytes, hipMemcpyDeviceToHost, c->stream)) != hipSuccess)
       return c->hip_fail(e, "hipMemcpyAsync(scores)");
-    if ((e = hipEventRecord(c->ev_done, c->stream)) != hipSuccess) return c->hip_fail(e, "hipEventRecord");
-    if (pend) return CSM_OK;
-    return wait_run(c, p);
+  } else {
+    csm::FinishArgs A = finish_args(P, D, G, skip_lists);
+    A.need_exact = (int32_t*)(dv + o_need);
+    A.exact_list = d_list;
+    A.done_ctr = (int32_t*)(dv + o_done);
+    A.host_flag = h_flag;
+    A.wide_windows = c->fast_wide_windows;
+    A.flag_value = flag_value;
+    if ((e = csm::launch_finish(A, d_scans, d_angles, (const double*)c->scores.p, h_out, nw, c->stream)) != hipSuccess)
+      return c->hip_fail(e, "finish_kernel");
+    if (c->profiling && (e = hipEventRecord(c->ev2, c->stream)) != hipSuccess) return c->hip_fail(e, "hipEventRecord");
+    p.device_finish = true;
+    p.fin_host = h_out;
+    p.host_flag = h_flag;
+    p.flag_value = flag_value;
   }
-  csm::FinishArgs A{};
-  A.n_cand = D.n_cand;
-  A.n_space = D.n_space;
-  A.step_cells = L.step_cells;
-  A.lin_tol = P.search_space_resolution / G.mres;
-  A.skip_lists = skip_lists | own_lists_skip(P.type);
-  A.need_exact = d_need;
-  A.exact_list = d_list;
-  A.done_ctr = d_done;
-  A.host_flag = h_flag;
-  A.wide_windows = c->fast_wide_windows;
-  A.flag_value = flag_value;
-  if ((e = csm::launch_finish(A, d_scans, d_angles, (const double*)c->scores.p, h_out, nw, c->stream)) != hipSuccess)
-    return c->hip_fail(e, "finish_kernel");
-  if (c->profiling && (e = hipEventRecord(c->ev2, c->stream)) != hipSuccess) return c->hip_fail(e, "hipEventRecord");
-  std::snprintf(p.fname, sizeof(p.fname), "finish_kernel<%lld>", (long long)D.n_cand);
-  p.finish_bytes = (double)nw * (double)D.n_cand * 8.0;
-  p.device_finish = true;
-  p.fin_host = h_out;
-  p.host_flag = h_flag;
-  p.flag_value = A.flag_value;
   if ((e = hipEventRecord(c->ev_done, c->stream)) != hipSuccess) return c->hip_fail(e, "hipEventRecord");
-  if (pend) return CSM_OK;
-  return wait_run(c, p);
+  return pend ? CSM_OK : wait_run(c, p);
 }
 
 // The fused fast finish (csm_tail.hpp); CSM_TAIL_FINISH=0 builds keep the
@@ -441,24 +486,56 @@ int run_windows_small(csm_ctx* c, const csm_param& P, const Dims& D, const Geome
 constexpr bool kTailFinish = CSM_TAIL_FINISH != 0;
 // (kTailMaxBeams, above which a level keeps the separate fast pass: csm_level_decision.hpp)
 
-int run_windows(csm_ctx* c, const csm_param& P, const Dims& D, const Geometry& G,
-                const std::vector<WindowPlan>& plans, const std::vector<int64_t>& pt_offsets,
-                const AngleEntry* angles, size_t n_angle_entries,
-                const std::vector<int32_t>& grid_index, BestPartial* best_out,
-                Finish mode, PendingRun* pend, int skip_lists, WinSpan sp) {
-  if (best_out) mode = Finish::kBest;
-  const int nw = (int)plans.size();
-  if (nw == 0) return CSM_OK;
-  const int w0 = sp.w1 < 0 ? 0 : sp.w0, w1 = sp.w1 < 0 ? nw : sp.w1;
-  const int nr = w1 - w0;  // windows scored by this call
-  const bool whole = w0 == 0 && w1 == nw && sp.score && sp.finish;
-  const double tp0 = c->profiling ? now_ms() : 0.0;  // host cost of the launch before its inputs (host:launch:prep)
-  if (!c->deferred.empty()) {  // the events below are recorded again
-    const int fst = flush_deferred(c);
-    if (fst != CSM_OK) return fst;
-  }
-  const double tp1 = c->profiling ? now_ms() : 0.0;  // (the deferred event reads are profiling's own cost)
-  if (c->profiling) c->account("host:launch:flush_events", (float)(tp1 - tp0), 0.0, 0.0);
+// One call of run_windows, handed from step to step: the call's arguments,
+// then what the steps decide and stage for the later ones.
+struct Launch {
+  csm_ctx* c;
+  const csm_param& P;
+  const Dims& D;
+  const Geometry& G;
+  const std::vector<WindowPlan>& plans;
+  const AngleEntry* angles;
+  size_t n_angle_entries;
+  Finish mode;
+  int skip_lists;
+  WinSpan sp;
+  int nw, w0, w1;  // the level's windows; this call scores [w0, w1)
+  bool whole;      // the whole level, scored and finished
+  double f;        // the window step in cells
+  LevelSummary S{};
+  LevelDecision dec{};
+  LaunchShape shape{};
+  csm::PhaseTable PT{};
+  bool sig = false;    // the host-signal finish (signalled_finish)
+  int64_t stride = 0;  // score_stride
+  LevelWork L{};
+  // the signalled finish's arguments (the fused finish's and the finish
+  // call's), where it reports, and the flags the host counts (profiling)
+  csm::FinishArgs SA{};
+  csm::FinishOut* sig_out = nullptr;
+  int32_t* d_done = nullptr;
+  const int32_t* flags_h = nullptr;
+  int n_flags = 0;
+  hipStream_t done_stream = nullptr;  // the stream the level's last work went to
+  int nr() const { return w1 - w0; }  // windows scored by this call
+  // csm_set_profiling(ctx, 2) times the scoring kernel alone: the finish's
+  // events on the kernel stream would add gaps to the value's region
+  bool time_fin() const { return c->profiling && !c->profile_first_level; }
+  // the steps, in run_windows' order
+  int validate(), decide(), level_work(const std::vector<int64_t>& pt_offsets, const std::vector<int32_t>& grid_index);
+  int stage_signalled(), stage_tail(), send_inputs(), scoring();
+  int launch_finish_timed(const csm::FinishArgs& A, csm::FinishOut* out, hipStream_t fs, bool fast_done);
+  int finish_scores_to_host(), finish_signalled(), finish_device(), finish_best(BestPartial* best_out);
+  void fill_pending(const char* kname, PendingRun& p);
+};
+
+// Validate the span and sum the level up (csm_level_decision.hpp): the
+// driver's summary, made from every window of the level before its first
+// call, or this whole-level call's own plans. Everything later that depends
+// on the windows (fixed point or fp64, the kernel family, its short forms,
+// the fused finish) is decided from it and never from this call's span, so
+// every call of a level decides alike.
+int Launch::validate() {
   if (!whole) {
     // (a part of a level cannot sum the level up itself: later windows' plans may not be written yet)
     bool ok = mode == Finish::kDevice && (sp.score || sp.finish) && 0 <= w0 && w0 < w1 && w1 <= nw &&
@@ -466,22 +543,9 @@ int run_windows(csm_ctx* c, const csm_param& P, const Dims& D, const Geometry& G
     for (int w = w0; ok && w < w1; ++w) ok = plans[(size_t)w].angle_off == (int64_t)w * D.n_angles;
     if (!ok) return c->fail(CSM_ERR_INVALID_ARG, "run_windows: bad window span");
   }
-  int st;
-  if ((st = ensure_int_grid(c)) != CSM_OK) return st;
-  // v2 column kernel: KT rows per lane, tiles balanced so at most a few rows idle
-  const int ktiles = (D.n_space + 15) / 16;
-  const int kt = (D.n_space + ktiles - 1) / ktiles;
-  const int64_t n_cols = (int64_t)D.n_angles * D.n_space;
-  const int64_t col_blocks = (n_cols + 63) / 64;
-  if (n_cols >= INT32_MAX) return c->fail(CSM_ERR_UNSUPPORTED, "window too large for one launch");
-  const double f = P.search_space_resolution / G.mres;
-  // The level summed up (csm_level_decision.hpp): the driver's, made from
-  // every window of the level before its first call, or this whole-level
-  // call's own plans. Everything below that depends on the windows (fixed
-  // point or fp64, the kernel family, its short forms, the fused finish) is
-  // decided from it and never from this call's span, so every call of a level
-  // decides alike.
-  LevelSummary S;
+  const int st = ensure_int_grid(c);
+  if (st != CSM_OK) return st;
+  if ((int64_t)D.n_angles * D.n_space >= INT32_MAX) return c->fail(CSM_ERR_UNSUPPORTED, "window too large for one launch");
   if (sp.level) {
     S = *sp.level;
     if (S.n_windows != nw) return c->fail(CSM_ERR_INVALID_ARG, "run_windows: the level's summary is of other windows");
@@ -489,298 +553,265 @@ int run_windows(csm_ctx* c, const csm_param& P, const Dims& D, const Geometry& G
     for (const WindowPlan& W : plans) level_summary_add(S, W.n_points, W.step, W.n_used, true);
     S.in_range = int_mode_ok(c, D, f, plans);
   }
+  return CSM_OK;
+}
+
+// The kernel families the level's window shape and step admit (LevelCaps),
+// the decision (level_decide) and the kernel's shape (launch_shape): the same
+// in every call of the level.
+// v4 row-segment kernel: fixed-point grid and an instantiation whose row
+// segment covers the x-span of a group, (n_space-1)*f cells (+2 for the
+// truncations); the kernel re-checks and recomputes exactly if exceeded.
+// v6 box kernel: whole-cell window step (use_int bounds |t| < 2^24 cells,
+// which its rounding margin needs), beam offsets that are 24-bit products
+// (LevelSummary::points_ok).
+// v7 phase kernel: sub-cell window step with an instantiated bucket shape.
+// v8 tiny-window kernel: a sub-cell step whose whole span is under one cell.
+int Launch::decide() {
   const bool use_int = c->int_ok && S.in_range;
-  if (whole && mode != Finish::kBest && use_int && small_launch(c, D, nw))
-    return run_windows_small(c, P, D, G, plans, pt_offsets, angles, n_angle_entries, grid_index,
-                             mode == Finish::kDevice, pend, skip_lists);
-  // v4 row-segment kernel: fixed-point grid and an instantiation whose row
-  // segment covers the x-span of a group, (n_space-1)*f cells (+2 for the
-  // truncations); the kernel re-checks and recomputes exactly if exceeded
-  int rows_sq = 0;
-  if (use_int && c->row_kernel && D.n_space <= 64) {
-    const double span = (double)(D.n_space - 1) * f;
-    // distinct columns of a group <= floor(span) + 2
-    rows_sq = csm::rows_pick_sq(D.n_space, (int)std::floor(span * (1.0 + 1e-9) + 1e-9) + 2);
-    if (c->info.size_x < 4 * rows_sq) rows_sq = 0;
-  }
-  // The kernel families the level's window shape and step admit (LevelCaps),
-  // then the decision (level_decide): the same in every call of the level.
-  // v6 box kernel: whole-cell window step (use_int bounds |t| < 2^24 cells,
-  // which its rounding margin needs), beam offsets that are 24-bit products
-  // (LevelSummary::points_ok).
-  // v7 phase kernel: sub-cell window step with an instantiated bucket shape.
-  // v8 tiny-window kernel: a sub-cell step whose whole span is under one cell.
-  const bool sig = signalled_finish(c, mode);
   const bool pad_ok = c->pitch >= c->info.size_x + csm::kGridiPadCols;
-  csm::PhaseTable PT{};
+  const int64_t gridi_cells = (int64_t)c->pitch * (c->info.size_y + csm::kGridiPadRows);
+  sig = signalled_finish(c, mode);
   LevelCaps K;
   K.int_grid = c->int_ok;
   K.tail_finish = kTailFinish && sig;
   K.box = c->box_kernel && f == 1.0 && csm::box_supported(D.n_space) && pad_ok;
   K.phase = use_int && c->phase_kernel && f < 1.0 && phase_table(f, D.n_space, c->phase_margin_log2, PT) &&
             csm::phase_supported(D.n_space, PT.cells, PT.nq) && pad_ok;
-  K.tiny = c->tiny_kernel && f < 1.0 && csm::tiny_supported(D.n_space, f) && pad_ok &&
-           (int64_t)c->pitch * (c->info.size_y + csm::kGridiPadRows) * 4 < INT32_MAX;
-  const LevelDecision dec = level_decide(S, K, w0, w1);
+  K.tiny = c->tiny_kernel && f < 1.0 && csm::tiny_supported(D.n_space, f) && pad_ok && gridi_cells * 4 < INT32_MAX;
+  dec = level_decide(S, K, w0, w1);
   if (!dec.valid) return c->fail(CSM_ERR_INVALID_ARG, "run_windows: bad window span");
-  const bool box_points_ok = dec.box_points_ok;
-  const bool box = dec.box;
-  if (box) rows_sq = 0;
+  ShapeFacts F;
+  F.best = mode == Finish::kBest;
+  if (use_int && c->row_kernel && D.n_space <= 64) {
+    const double span = (double)(D.n_space - 1) * f;
+    // distinct columns of a group <= floor(span) + 2
+    F.rows_sq = csm::rows_pick_sq(D.n_space, (int)std::floor(span * (1.0 + 1e-9) + 1e-9) + 2);
+    if (c->info.size_x < 4 * F.rows_sq) F.rows_sq = 0;
+  }
   // v11: the box read through the grid's palette (one byte per cell), pairs
   // of equal-count runs over the strip copies (palettes of <= 16 values);
   // otherwise the v6 kernel reads gridi
-  bool box_pal = false;
-  if (box && c->pair_kernel && csm::box_pair_supported(D.n_space)) {
+  int st;
+  if (dec.box && c->pair_kernel && csm::box_pair_supported(D.n_space)) {
     if ((st = ensure_palette(c)) != CSM_OK) return st;
-    box_pal = c->pal_n > 0 && (int64_t)c->pitch * (c->info.size_y + csm::kGridiPadRows) <= INT32_MAX;
+    F.pair_ok = c->pal_n > 0 && gridi_cells <= INT32_MAX && c->pal_strips_ok;
   }
-  const bool box_pair = box_pal && c->pal_strips_ok;
-  // v6 over 16 x 16 tiles: the argmax of a one-cell-step window wider than 16
-  // (loop-closure windows), in place of the column kernel's dword gathers
-  const int tile_n = (D.n_space + 15) / 16;
-  const bool box_tiled = !box && best_out && use_int && box_points_ok && c->box_kernel && f == 1.0 && D.n_space > 16 &&
-                         c->pitch >= c->info.size_x + csm::kGridiPadCols &&
-                         (int64_t)nw * tile_n * tile_n * D.n_angles <= INT32_MAX;
-  if (box_tiled) rows_sq = 0;
-  const bool phase = dec.phase;
-  if (phase) rows_sq = 0;
-  if (phase && c->phase_strips && (st = ensure_istrips(c)) != CSM_OK) return st;
-  const bool phase_st = phase && c->phase_strips && c->istrips_ok;
-  const bool tiny = dec.tiny;
-  if (tiny) rows_sq = 0;
-  const int64_t rows_groups = rows_sq ? 64 / D.n_space : 1;
-  const int64_t bps = box_tiled ? (int64_t)tile_n * tile_n * D.n_angles
-                      : (box || phase || tiny) ? D.n_angles
-                      : rows_sq ? (D.n_angles + rows_groups - 1) / rows_groups
-                                : col_blocks * ktiles;
-  if (bps * nr > INT32_MAX) return c->fail(CSM_ERR_UNSUPPORTED, "window too large for one launch");
+  const int64_t tile_n = (D.n_space + 15) / 16;
+  F.tiled_ok = c->box_kernel && f == 1.0 && pad_ok && (int64_t)nw * tile_n * tile_n * D.n_angles <= INT32_MAX;
+  if (dec.phase && c->phase_strips && (st = ensure_istrips(c)) != CSM_OK) return st;
+  shape = launch_shape(dec, D.n_angles, D.n_space, F);
+  if (shape.bps * nr() > INT32_MAX) return c->fail(CSM_ERR_UNSUPPORTED, "window too large for one launch");
+  stride = score_stride(c, D, mode);
+  return CSM_OK;
+}
 
-  hipError_t e;
-  if ((e = c->h_sw.ensure((size_t)nw * sizeof(ScanWork))) != hipSuccess) return c->hip_fail(e, "hipHostMalloc(scans)");
-  ScanWork* sw = (ScanWork*)c->h_sw.p;  // pinned staging
-  // Host-signal finish (the device finish with its fast pass): FinishOut goes
-  // straight to coherent pinned memory and the pass that ends last sets a flag
-  // the host spins on; the scoring kernel clears the flagged-window count
-  // (sig, above).
-  // The fused fast finish (csm_tail.hpp): the level's scoring launches finish
-  // their windows themselves, no fast-pass launch: every window in
-  // fixed-point range, a kernel that carries the finish, and no window
-  // summing more than kTailMaxBeams beams. The decision is level_decide's,
-  // from the summary of the whole level, so a level's spans and its
-  // finish-only call all reach it whatever windows each of them holds and
-  // whichever of the level's plans were written when it was made (until r06
-  // each call took the maxima over the plans written so far, zeros elsewhere:
-  // a first span of short scans fused its finish, and the later calls of a
-  // level with a longer scan ran the separate fast pass over every window,
-  // the first span's a second time, with level_ctr left part-counted). Each
-  // window's scores then start on a 128-byte line of their own (no line is
-  // shared by two windows: a finisher's sc1 loads never find a line another
-  // window's finisher brought into its L2 before that window's scores were
-  // stored).
-  // Only for short scoring waves: each wave waits for its write-through score
-  // stores before counting in, which at B = 1081 costs the scoring launches
-  // as much as the separate fast pass costs (r05: +55 / +30 / +43 us on the
-  // box / phase / tiny launches against -32 / -31 / -29 us of fast passes);
-  // at B = 109 the host gets each level's signal ~50 us earlier and the step
-  // shortens.
-  const bool tail = dec.tail;
-  const int64_t stride = score_stride(c, D, mode);
+// This call's ScanWork in the pinned staging, and the level's LevelWork.
+int Launch::level_work(const std::vector<int64_t>& pt_offsets, const std::vector<int32_t>& grid_index) {
+  const hipError_t e = c->h_sw.ensure((size_t)nw * sizeof(ScanWork));
+  if (e != hipSuccess) return c->hip_fail(e, "hipHostMalloc(scans)");
+  ScanWork* sw = (ScanWork*)c->h_sw.p;
   // the plan pass may have filled this call's ScanWork already (WinSpan::sw_ready:
   // level_plan_one, into this slot's staging, at this stride)
   if (sp.score && !(sp.sw_ready && sp.sw_stride == stride && (const void*)sp.sw_ready == (const void*)sw))
     fill_scan_work(D, plans, pt_offsets, grid_index, sw, (size_t)w0, (size_t)w1, stride);
-  LevelWork L = make_level_work(c, P, D, G, nr, use_int);
-  L.blocks_per_scan = box_tiled ? D.n_angles : (int32_t)bps;  // per (window, tile) when tiled
+  L = make_level_work(c, P, D, G, nr(), dec.use_int);
+  const bool tiled = shape.kernel == ScoreKernel::kBoxTiled;
+  L.blocks_per_scan = tiled ? D.n_angles : (int32_t)shape.bps;  // per (window, tile) when tiled
   // level-wide, not this span's: the pair and phase kernels' short forms hold
   // for any window of at most that many beams, and one form per level keeps a
   // level's spans on one kernel instantiation
   L.max_n_used = dec.max_n_used;
-  L.tile_n = box_tiled ? tile_n : 0;
-  if (box_pair) {
+  L.tile_n = tiled ? shape.ktiles : 0;
+  if (shape.kernel == ScoreKernel::kBoxPair) {
+    const csm::StripGeom SG = csm::strip_geom(c->info.size_x, c->info.size_y);
     L.pal_n = c->pal_n;
     L.pal_grid = (const uint8_t*)c->pal_grid.p;
     L.pal_vals = (const int32_t*)c->pal_vals.p;
     L.pal_stride = (int64_t)c->pitch * (c->info.size_y + csm::kGridiPadRows);
+    L.pal_strips = (const uint8_t*)c->pal_strips.p;
+    L.strip_bytes = (int32_t)SG.strip_bytes;
+    L.strip_copy_bytes = (int32_t)SG.copy_bytes;
+    L.strip_grid_bytes = SG.grid_bytes;
   }
-  if (phase_st) {
+  if (shape.kernel == ScoreKernel::kPhase && c->phase_strips && c->istrips_ok) {
     const csm::StripGeom SG = csm::istrip_geom(c->info.size_x, c->info.size_y);
     L.istrips = (const int32_t*)c->istrips.p;
     L.istrip_bytes = (int32_t)SG.strip_bytes;
     L.istrip_copy_bytes = (int32_t)SG.copy_bytes;
     L.istrip_grid_bytes = SG.grid_bytes;
   }
-  if (box_pair) {
-    const csm::StripGeom SG = csm::strip_geom(c->info.size_x, c->info.size_y);
-    L.pal_strips = (const uint8_t*)c->pal_strips.p;
-    L.strip_bytes = (int32_t)SG.strip_bytes;
-    L.strip_copy_bytes = (int32_t)SG.copy_bytes;
-    L.strip_grid_bytes = SG.grid_bytes;
-  }
-  L.n_cols = (int32_t)n_cols;
-  L.ktiles = ktiles;
-  L.col_blocks = (int32_t)col_blocks;
+  L.n_cols = (int32_t)shape.n_cols;
+  L.ktiles = shape.ktiles;
+  L.col_blocks = (int32_t)shape.col_blocks;
+  return CSM_OK;
+}
 
-  int32_t *d_done = nullptr, *d_need = nullptr, *d_list = nullptr;
-  int32_t sig_tag = 0;
-  if (sig) {
-    // done counter (0) | the fused finish's level counter (32) | need[nw] |
-    // list {count, tag, windows[nw]}
-    const size_t o_need = 64, o_list = (o_need + (size_t)nw * 4 + 7) & ~(size_t)7;  // {count, tag}: 8 bytes
-    const size_t dbytes = o_list + (size_t)(nw + 2) * 4;
-    if (dbytes > c->fin_sig.cap) {  // the counters start at zero; each launch leaves them at zero
-      if ((e = c->fin_sig.ensure(dbytes)) != hipSuccess) return c->hip_fail(e, "hipMalloc(finish signal)");
-      if ((e = hipMemsetAsync(c->fin_sig.p, 0, c->fin_sig.cap, c->stream)) != hipSuccess)
-        return c->hip_fail(e, "hipMemsetAsync(finish signal)");
-    }
-    d_done = (int32_t*)c->fin_sig.p;
-    d_need = (int32_t*)((char*)c->fin_sig.p + o_need);
-    d_list = (int32_t*)((char*)c->fin_sig.p + o_list);
-    // The level's first scoring call's block 0 clears the list to {0, tag}
-    // (with the fused finish, the windows' finishers of every span append
-    // after it, csm_tail.hpp)
-    L.clear_word = (sp.score && w0 == 0) ? d_list : nullptr;
-    // A fresh tag per level: its first scoring call draws it, later spans and
-    // the finish (the level's last call, which may score nothing itself) use
-    // the slot's latest one as their flag value. The slot's previous exact
-    // pass (on x_stream) may still be queued when this level's scoring and
-    // fast pass reuse the list: it had no windows (or the host would not have
-    // gone on), and it finds another tag.
-    if (sp.score && w0 == 0) {
-      c->list_tag = (int32_t)(++c->flag_seq & 0x7FFFFFFF);
-      if (c->list_tag == 0) c->list_tag = (int32_t)(++c->flag_seq & 0x7FFFFFFF);
-    }
-    sig_tag = c->list_tag;
-    L.clear_tag = sig_tag;
-  }
-  // the signalled finish's arguments (the fused finish's and the finish call's)
-  csm::FinishArgs SA{};
-  csm::FinishOut* sig_out = nullptr;
-  int32_t* sig_flag = nullptr;
-  int32_t* sig_fast = nullptr;
-  const int32_t* flags_h = nullptr;
-  int n_flags = 0;
-  if (sig) {
-    SA.n_cand = D.n_cand;
-    SA.score_stride = stride;
-    SA.n_space = D.n_space;
-    SA.step_cells = L.step_cells;
-    SA.lin_tol = P.search_space_resolution / G.mres;
-    SA.skip_lists = skip_lists | own_lists_skip(P.type);
-    SA.need_exact = d_need;
-    SA.exact_list = d_list;
-    SA.done_ctr = d_done;
-    SA.wide_windows = c->fast_wide_windows;
-    // FinishOut[nw] | need[nw] (profiling: the flags the host counts) | flag
-    const size_t out_need = ((size_t)nw * sizeof(csm::FinishOut) + 63) & ~(size_t)63;
-    const size_t out_flag = (out_need + (size_t)nw * sizeof(int32_t) + 63) & ~(size_t)63;
-    if (out_flag + 64 > c->h_fin_sig.cap) {
-      if ((e = c->h_fin_sig.ensure(std::max<size_t>(out_flag + 64, 64 * 1024), hipHostMallocCoherent)) != hipSuccess)
-        return c->hip_fail(e, "hipHostMalloc(finish signal)");
-      std::memset(c->h_fin_sig.p, 0, c->h_fin_sig.cap);
-    }
-    sig_out = (csm::FinishOut*)c->h_fin_sig.p;
-    sig_flag = (int32_t*)((char*)c->h_fin_sig.p + out_flag);
-    if (c->profiling && !c->profile_first_level) {  // the fast pass's flags to the host: finish:exact_windows
-      SA.need_exact = (int32_t*)((char*)c->h_fin_sig.p + out_need);
-      flags_h = SA.need_exact;
-      n_flags = nw;
-    }
-    SA.host_flag = sig_flag;
-    SA.flag_value = sig_tag;
-    SA.host_fast_flag = (c->early_complete && c->early_now) ? sig_flag + 8 : nullptr;  // same 64-byte slot
-    sig_fast = SA.host_fast_flag;
-  }
-  if (tail) {
-    L.tail.on = 1;
-    L.tail.n_windows = nw;
-    // the window counters: a buffer of their own, zeroed when it grows and
-    // left at zero by every window's finisher (need and the list, whose
-    // offsets move with nw, hold stale values)
-    if ((size_t)nw * sizeof(int32_t) > c->win_ctr.cap) {
-      if ((e = c->win_ctr.ensure((size_t)nw * sizeof(int32_t))) != hipSuccess)
-        return c->hip_fail(e, "hipMalloc(window counters)");
-      if ((e = hipMemsetAsync(c->win_ctr.p, 0, c->win_ctr.cap, c->stream)) != hipSuccess)
-        return c->hip_fail(e, "hipMemsetAsync(window counters)");
-    }
-    L.tail.win_ctr = (int32_t*)c->win_ctr.p;
-    L.tail.level_ctr = d_done + 8;
-    L.tail.out = sig_out;
-    L.tail.A = SA;
-    if ((e = c->ang_max.ensure((size_t)nw * (size_t)D.n_angles * sizeof(double))) != hipSuccess)
-      return c->hip_fail(e, "hipMalloc(angle maxima)");
-    L.tail.ang_max = (double*)c->ang_max.p;
-    if (sp.score && w0 == 0 && c->tail_open) {  // an earlier level of this slot stopped between spans
-      if ((e = hipMemsetAsync(c->fin_sig.p, 0, c->fin_sig.cap, c->stream)) != hipSuccess ||
-          (e = hipMemsetAsync(c->win_ctr.p, 0, c->win_ctr.cap, c->stream)) != hipSuccess)
-        return c->hip_fail(e, "hipMemsetAsync(stale tail counters)");
-      c->tail_open = false;
-    }
-  }
+// The signalled finish's device buffer: done counter (0) | the fused finish's
+// level counter (32) | need[nw] (64) | list {count, tag, windows[nw]}.
+// csm_tail.hpp and csm_finish.hip rely on level_ctr = done + 8 (int32) and on
+// the list's {count, tag} being one 8-aligned word.
+struct SigCarve {
+  size_t need, tail, bytes;  // tail: the device's list, the host's flag
+};
+SigCarve sig_dev_carve(int nw) {
+  const size_t o_need = 64, o_list = (o_need + (size_t)nw * 4 + 7) & ~(size_t)7;
+  return {o_need, o_list, o_list + (size_t)(nw + 2) * 4};
+}
+// ... and its coherent host buffer: FinishOut[nw] | need[nw] (profiling: the
+// flags the host counts) | flag, with host_fast_flag = flag + 8 (int32) in the
+// same 64-byte slot.
+SigCarve sig_host_carve(int nw) {
+  const size_t o_need = ((size_t)nw * sizeof(csm::FinishOut) + 63) & ~(size_t)63;
+  const size_t o_flag = (o_need + (size_t)nw * sizeof(int32_t) + 63) & ~(size_t)63;
+  return {o_need, o_flag, o_flag + 64};
+}
 
-  if ((e = c->scans.ensure((size_t)nw * sizeof(ScanWork))) != hipSuccess) return c->hip_fail(e, "hipMalloc(scans)");
-  if ((e = c->angles.ensure(n_angle_entries * sizeof(AngleEntry))) != hipSuccess) return c->hip_fail(e, "hipMalloc(angles)");
-  const double tl0 = c->profiling ? now_ms() : 0.0;  // host cost of the launch, by phase
-  if (c->profiling) c->account("host:launch:prep", (float)(tl0 - tp1), 0.0, 0.0);
-  if (sp.score) {  // this call's windows and angle rows
-    const size_t a0 = whole ? 0 : (size_t)w0 * D.n_angles;
-    const size_t na = whole ? n_angle_entries : (size_t)nr * D.n_angles;
-    // (copied on the kernel stream itself instead, r03 A/B: 7.05-7.07 vs
-    // 7.14-7.23 G scorings/s)
-    hipStream_t is = c->h2d;
-    if ((e = hipMemcpyAsync((ScanWork*)c->scans.p + w0, sw + w0, (size_t)nr * sizeof(ScanWork), hipMemcpyHostToDevice,
-                            is)) != hipSuccess)
-      return c->hip_fail(e, "hipMemcpyAsync(scans)");
-    if (!(sp.dev_trig && sp.rows_gen) &&
-        (e = hipMemcpyAsync((AngleEntry*)c->angles.p + a0, angles + a0, na * sizeof(AngleEntry), hipMemcpyHostToDevice,
-                            is)) != hipSuccess)
-      return c->hip_fail(e, "hipMemcpyAsync(angles)");
-    if (sp.dev_trig) {  // the rows' cos/sin (the plan left them to the device)
-      const double* tab = libm_sincos_table();
-      if (!tab) return c->fail(CSM_ERR_UNSUPPORTED, "run_windows: device trig without the libm table");
-      if (!c->trig_tab.p) {
-        if ((e = c->trig_tab.ensure(csm::libm::kSincosTableDoubles * sizeof(double))) != hipSuccess)
-          return c->hip_fail(e, "hipMalloc(sincos table)");
-        if ((e = hipMemcpyAsync(c->trig_tab.p, tab, csm::libm::kSincosTableDoubles * sizeof(double),
-                                hipMemcpyHostToDevice, is)) != hipSuccess)
-          return c->hip_fail(e, "hipMemcpyAsync(sincos table)");
-      }
-      if (sp.rows_gen)  // the rows whole from the windows' ScanWork (copied above)
-        e = csm::launch_angle_rows((const ScanWork*)c->scans.p + w0, nr, D.n_angles, (P.search_angle_offset * 2) / 2,
-                                   P.search_angle_resolution, (AngleEntry*)c->angles.p, (const double*)c->trig_tab.p, is);
-      else
-        e = csm::launch_angle_trig((AngleEntry*)c->angles.p + a0, (int64_t)na, (const double*)c->trig_tab.p, is);
-      if (e != hipSuccess) return c->hip_fail(e, "angle rows kernel");
-      // launches: the launches with device rows; bytes: the rows' copy saved
-      if (c->profiling) c->account(sp.rows_gen ? "host:trig_rows:gen" : "host:trig_rows", 0.0f,
-                                   (double)na * sizeof(AngleEntry), 0.0);
-    }
-    if ((e = hipEventRecord(c->ev_in, c->h2d)) != hipSuccess || (e = hipStreamWaitEvent(c->stream, c->ev_in, 0)) != hipSuccess)
-      return c->hip_fail(e, "inputs event");
+// Host-signal finish (the device finish with its fast pass): FinishOut goes
+// straight to coherent pinned memory and the pass that ends last sets a flag
+// the host spins on; the scoring kernel clears the flagged-window count.
+int Launch::stage_signalled() {
+  int st;
+  const SigCarve dv = sig_dev_carve(nw), hv = sig_host_carve(nw);
+  if ((st = ensure_zeroed(c, c->fin_sig, dv.bytes, dv.bytes, false, "finish signal buffer")) != CSM_OK) return st;
+  d_done = (int32_t*)c->fin_sig.p;
+  int32_t* d_list = (int32_t*)((char*)c->fin_sig.p + dv.tail);
+  // The level's first scoring call's block 0 clears the list to {0, tag}
+  // (with the fused finish, the windows' finishers of every span append
+  // after it, csm_tail.hpp)
+  L.clear_word = (sp.score && w0 == 0) ? d_list : nullptr;
+  // A fresh tag per level: its first scoring call draws it, later spans and
+  // the finish (the level's last call, which may score nothing itself) use
+  // the slot's latest one as their flag value. The slot's previous exact
+  // pass (on x_stream) may still be queued when this level's scoring and
+  // fast pass reuse the list: it had no windows (or the host would not have
+  // gone on), and it finds another tag.
+  if (sp.score && w0 == 0) c->list_tag = draw_tag(c);
+  L.clear_tag = c->list_tag;
+  SA = finish_args(P, D, G, skip_lists);
+  SA.score_stride = stride;
+  SA.need_exact = (int32_t*)((char*)c->fin_sig.p + dv.need);
+  SA.exact_list = d_list;
+  SA.done_ctr = d_done;
+  SA.wide_windows = c->fast_wide_windows;
+  if ((st = ensure_host_zeroed(c, c->h_fin_sig, hv.bytes, "hipHostMalloc(finish signal)")) != CSM_OK) return st;
+  sig_out = (csm::FinishOut*)c->h_fin_sig.p;
+  if (c->profiling && !c->profile_first_level) {  // the fast pass's flags to the host: finish:exact_windows
+    SA.need_exact = (int32_t*)((char*)c->h_fin_sig.p + hv.need);
+    flags_h = SA.need_exact;
+    n_flags = nw;
   }
+  SA.host_flag = (int32_t*)((char*)c->h_fin_sig.p + hv.tail);
+  SA.flag_value = c->list_tag;
+  SA.host_fast_flag = (c->early_complete && c->early_now) ? SA.host_flag + 8 : nullptr;  // same 64-byte slot
+  return CSM_OK;
+}
 
-  // algorithmic traffic: one fp32 grid read per summed beam per candidate
-  double beams = 0.0;
-  for (const WindowPlan& W : plans) beams += (double)W.n_used;
-  const double alg_bytes = beams * (double)D.n_cand * 4.0;
-  const double scorings = (double)nw * (double)D.n_cand;
-  char kname[48];
-  if (box_pair)
-    std::snprintf(kname, sizeof(kname), "score_box_pair_kernel<%d,%s>", D.n_space, best_out ? "best" : "all");
-  else if (box)
-    std::snprintf(kname, sizeof(kname), "score_box_kernel<%d,%s>", D.n_space, best_out ? "best" : "all");
-  else if (box_tiled)
-    std::snprintf(kname, sizeof(kname), "score_box_kernel<16,best,tiles>");
-  else if (phase)
-    std::snprintf(kname, sizeof(kname), "score_phase_kernel<%d,%s>", D.n_space, best_out ? "best" : "all");
-  else if (tiny)
-    std::snprintf(kname, sizeof(kname), "score_tiny_kernel<%d,%s>", D.n_space, best_out ? "best" : "all");
-  else if (rows_sq)
-    std::snprintf(kname, sizeof(kname), "score_rowsd_kernel<%d,%d,%s>", D.n_space, rows_sq,
-                  best_out ? "best" : "all");
-  else
-    std::snprintf(kname, sizeof(kname), "score_cols_kernel<%d,%s,%s>", kt, use_int ? "int" : "f64",
-                  best_out ? "best" : "all");
-  const double tl1 = c->profiling ? now_ms() : 0.0;
+// The fused fast finish (csm_tail.hpp): the level's scoring launches finish
+// their windows themselves, no fast-pass launch: every window in
+// fixed-point range, a kernel that carries the finish, and no window
+// summing more than kTailMaxBeams beams. The decision is level_decide's,
+// from the summary of the whole level, so a level's spans and its
+// finish-only call all reach it whatever windows each of them holds and
+// whichever of the level's plans were written when it was made (until r06
+// each call took the maxima over the plans written so far, zeros elsewhere:
+// a first span of short scans fused its finish, and the later calls of a
+// level with a longer scan ran the separate fast pass over every window,
+// the first span's a second time, with level_ctr left part-counted). Each
+// window's scores then start on a 128-byte line of their own (no line is
+// shared by two windows: a finisher's sc1 loads never find a line another
+// window's finisher brought into its L2 before that window's scores were
+// stored).
+// Only for short scoring waves: each wave waits for its write-through score
+// stores before counting in, which at B = 1081 costs the scoring launches
+// as much as the separate fast pass costs (r05: +55 / +30 / +43 us on the
+// box / phase / tiny launches against -32 / -31 / -29 us of fast passes);
+// at B = 109 the host gets each level's signal ~50 us earlier and the step
+// shortens.
+int Launch::stage_tail() {
+  hipError_t e;
+  L.tail.on = 1;
+  L.tail.n_windows = nw;
+  // the window counters: a buffer of their own, zeroed when it grows and
+  // left at zero by every window's finisher (need and the list, whose
+  // offsets move with nw, hold stale values)
+  const size_t cbytes = (size_t)nw * sizeof(int32_t);
+  const int st = ensure_zeroed(c, c->win_ctr, cbytes, cbytes, false, "window counters");
+  if (st != CSM_OK) return st;
+  L.tail.win_ctr = (int32_t*)c->win_ctr.p;
+  L.tail.level_ctr = d_done + 8;
+  L.tail.out = sig_out;
+  L.tail.A = SA;
+  if ((e = c->ang_max.ensure((size_t)nw * (size_t)D.n_angles * sizeof(double))) != hipSuccess)
+    return c->hip_fail(e, "hipMalloc(angle maxima)");
+  L.tail.ang_max = (double*)c->ang_max.p;
+  if (sp.score && w0 == 0 && c->tail_open) {  // an earlier level of this slot stopped between spans
+    if ((e = hipMemsetAsync(c->fin_sig.p, 0, c->fin_sig.cap, c->stream)) != hipSuccess ||
+        (e = hipMemsetAsync(c->win_ctr.p, 0, c->win_ctr.cap, c->stream)) != hipSuccess)
+      return c->hip_fail(e, "hipMemsetAsync(stale tail counters)");
+    c->tail_open = false;
+  }
+  return CSM_OK;
+}
+
+// This call's windows and angle rows, on h2d (copied on the kernel stream
+// itself instead, r03 A/B: 7.05-7.07 vs 7.14-7.23 G scorings/s); then the
+// inputs' event and the kernel stream's wait on it.
+int Launch::send_inputs() {
+  const ScanWork* sw = (const ScanWork*)c->h_sw.p;
+  const size_t a0 = whole ? 0 : (size_t)w0 * D.n_angles;
+  const size_t na = whole ? n_angle_entries : (size_t)nr() * D.n_angles;
+  hipError_t e;
+  hipStream_t is = c->h2d;
+  if ((e = hipMemcpyAsync((ScanWork*)c->scans.p + w0, sw + w0, (size_t)nr() * sizeof(ScanWork), hipMemcpyHostToDevice,
+                          is)) != hipSuccess)
+    return c->hip_fail(e, "hipMemcpyAsync(scans)");
+  if (!(sp.dev_trig && sp.rows_gen) &&
+      (e = hipMemcpyAsync((AngleEntry*)c->angles.p + a0, angles + a0, na * sizeof(AngleEntry), hipMemcpyHostToDevice,
+                          is)) != hipSuccess)
+    return c->hip_fail(e, "hipMemcpyAsync(angles)");
+  if (sp.dev_trig) {  // the rows' cos/sin (the plan left them to the device)
+    const int st = ensure_trig_table(c, is);
+    if (st != CSM_OK) return st;
+    if (sp.rows_gen)  // the rows whole from the windows' ScanWork (copied above)
+      e = csm::launch_angle_rows((const ScanWork*)c->scans.p + w0, nr(), D.n_angles, (P.search_angle_offset * 2) / 2,
+                                 P.search_angle_resolution, (AngleEntry*)c->angles.p, (const double*)c->trig_tab.p, is);
+    else
+      e = csm::launch_angle_trig((AngleEntry*)c->angles.p + a0, (int64_t)na, (const double*)c->trig_tab.p, is);
+    if (e != hipSuccess) return c->hip_fail(e, "angle rows kernel");
+    // launches: the launches with device rows; bytes: the rows' copy saved
+    if (c->profiling) c->account(sp.rows_gen ? "host:trig_rows:gen" : "host:trig_rows", 0.0f,
+                                 (double)na * sizeof(AngleEntry), 0.0);
+  }
+  if ((e = hipEventRecord(c->ev_in, c->h2d)) != hipSuccess || (e = hipStreamWaitEvent(c->stream, c->ev_in, 0)) != hipSuccess)
+    return c->hip_fail(e, "inputs event");
+  return CSM_OK;
+}
+
+// The one place a shape becomes a launch. All-scores and best mode differ in
+// which of d_out / d_partials is null.
+hipError_t launch_score(const LaunchShape& s, const LevelWork& L, const csm::PhaseTable& PT, const ScanWork* d_sw,
+                        const double* d_pts, const AngleEntry* d_ang, double* d_out, BestPartial* d_partials,
+                        hipStream_t stream) {
+  switch (s.kernel) {
+    case ScoreKernel::kBoxPair:
+      return csm::launch_score_box_pair(L, d_sw, d_pts, d_ang, d_out, d_partials, s.n_space, stream);
+    case ScoreKernel::kBox: return csm::launch_score_box(L, d_sw, d_pts, d_ang, d_out, d_partials, s.n_space, stream);
+    case ScoreKernel::kBoxTiled: return csm::launch_score_box(L, d_sw, d_pts, d_ang, d_out, d_partials, 16, stream);
+    case ScoreKernel::kPhase:
+      return csm::launch_score_phase(L, PT, d_sw, d_pts, d_ang, d_out, d_partials, s.n_space, stream);
+    case ScoreKernel::kTiny: return csm::launch_score_tiny(L, d_sw, d_pts, d_ang, d_out, d_partials, s.n_space, stream);
+    case ScoreKernel::kRows:
+      return csm::launch_score_rows(L, d_sw, d_pts, d_ang, d_out, d_partials, s.n_space, s.rows_sq, stream);
+    case ScoreKernel::kCols: return csm::launch_score_cols(L, d_sw, d_pts, d_ang, d_out, d_partials, s.kt, stream);
+  }
+  return hipErrorInvalidValue;
+}
+
+// The marker and the profiling events, then this call's scoring launch.
+int Launch::scoring() {
+  const bool best = mode == Finish::kBest;
+  hipError_t e;
   // (a signalled launch lets the host go on before its exact pass on
   // x_stream has retired; the list's tag, LevelWork::clear_tag, makes a stale
   // pass exit, so the slot's next scoring need not wait for it)
@@ -800,192 +831,197 @@ int run_windows(csm_ctx* c, const csm_param& P, const Dims& D, const Geometry& G
     if ((e = hipEventRecord(c->ev_g1, c->stream)) != hipSuccess) return c->hip_fail(e, "hipEventRecord");
     c->span_gap = true;
   }
-
-  // csm_set_profiling(ctx, 2) times the scoring kernel alone: the finish's
-  // events on the kernel stream would add gaps to the value's region
-  const bool time_fin = c->profiling && !c->profile_first_level;
-  int32_t sig_value = 0;
-  hipStream_t done_stream = c->d2h;
-  double tl2 = 0.0;
-  if (mode != Finish::kBest) {
-    const size_t bytes = (size_t)nw * (size_t)D.n_cand * sizeof(double);
-    if ((e = c->scores.ensure((size_t)nw * (size_t)stride * sizeof(double))) != hipSuccess)
-      return c->hip_fail(e, "hipMalloc(scores)");
-    const ScanWork* d_sw = (const ScanWork*)c->scans.p + w0;
-    if (!sp.score)
-      e = hipSuccess;  // scored by earlier calls
-    else if (box_pair)
-      e = csm::launch_score_box_pair(L, d_sw, (const double*)c->pts.p, (const AngleEntry*)c->angles.p,
-                                     (double*)c->scores.p, nullptr, D.n_space, c->stream);
-    else if (box)
-      e = csm::launch_score_box(L, d_sw, (const double*)c->pts.p,
-                                (const AngleEntry*)c->angles.p, (double*)c->scores.p, nullptr, D.n_space,
-                                c->stream);
-    else if (phase)
-      e = csm::launch_score_phase(L, PT, d_sw, (const double*)c->pts.p, (const AngleEntry*)c->angles.p,
-                                  (double*)c->scores.p, nullptr, D.n_space, c->stream);
-    else if (tiny)
-      e = csm::launch_score_tiny(L, d_sw, (const double*)c->pts.p, (const AngleEntry*)c->angles.p,
-                                 (double*)c->scores.p, nullptr, D.n_space, c->stream);
-    else if (rows_sq)
-      e = csm::launch_score_rows(L, d_sw, (const double*)c->pts.p, (const AngleEntry*)c->angles.p,
-                                 (double*)c->scores.p, nullptr, D.n_space, rows_sq, c->stream);
-    else
-      e = csm::launch_score_cols(L, d_sw, (const double*)c->pts.p, (const AngleEntry*)c->angles.p,
-                                 (double*)c->scores.p, nullptr, kt, c->stream);
-    if (e != hipSuccess) return c->hip_fail(e, "score kernel");
-    if (tail && sp.score) c->tail_open = w1 < nw;  // the level's last window is out: its counters close
-    if (sp.score && c->profiling && (e = hipEventRecord(c->ev1, c->stream)) != hipSuccess)
-      return c->hip_fail(e, "hipEventRecord");
-    if (sp.score && !sp.finish && w0 == 0 && c->profiling && (e = hipEventRecord(c->ev_g0, c->stream)) != hipSuccess)
-      return c->hip_fail(e, "hipEventRecord");  // the first span's end
-    if (c->profiling) {
-      c->account("host:launch:inputs", (float)(tl1 - tl0), 0.0, 0.0);
-      c->account("host:launch:score", (float)(now_ms() - tl1), 0.0, 0.0);
-    }
-    if (!sp.finish) return CSM_OK;  // the finish comes with the level's last call
-    tl2 = c->profiling ? now_ms() : 0.0;
-    if (mode == Finish::kScoresToHost) {
-      if ((e = c->h_scores.ensure(bytes)) != hipSuccess) return c->hip_fail(e, "hipHostMalloc(scores)");
-      if ((e = hipEventRecord(c->ev_k, c->stream)) != hipSuccess || (e = hipStreamWaitEvent(c->d2h, c->ev_k, 0)) != hipSuccess)
-        return c->hip_fail(e, "kernels event");
-      if ((e = hipMemcpyAsync(c->h_scores.p, c->scores.p, bytes, hipMemcpyDeviceToHost, c->d2h)) != hipSuccess)
-        return c->hip_fail(e, "hipMemcpyAsync(scores)");
-    } else if (sig) {
-      sig_value = SA.flag_value;
-      done_stream = c->x_stream ? c->x_stream : c->stream;
-      // with the fused finish the scoring launches did the fast pass's work:
-      // only the exact pass is launched, after them
-      if ((e = csm::launch_finish(SA, (const ScanWork*)c->scans.p, (const AngleEntry*)c->angles.p,
-                                  (const double*)c->scores.p, sig_out, nw, c->stream, done_stream, c->ev_fast,
-                                  tail)) != hipSuccess)
-        return c->hip_fail(e, "finish_kernel");
-      if (time_fin && done_stream != c->stream && (e = hipEventRecord(c->ev_ft, c->stream)) != hipSuccess)
-        return c->hip_fail(e, "hipEventRecord");
-      if (time_fin && (e = hipEventRecord(c->ev2, done_stream)) != hipSuccess) return c->hip_fail(e, "hipEventRecord");
-    } else {
-      csm::FinishArgs A{};
-      A.n_cand = D.n_cand;
-      A.n_space = D.n_space;
-      A.step_cells = L.step_cells;
-      A.lin_tol = P.search_space_resolution / G.mres;
-      A.skip_lists = skip_lists | own_lists_skip(P.type);
-      const size_t fbytes = (size_t)nw * sizeof(csm::FinishOut);
-      // + one "needs the exact sort" flag per window (fast finish, csm_finish.hip)
-      // + the flags' compacted list (count, then windows)
-      const size_t lbytes = ((size_t)nw * sizeof(int32_t) + 7) & ~(size_t)7;  // the list's {count, tag}: 8-aligned
-      if ((e = c->fin.ensure(fbytes + lbytes + (size_t)(nw + 2) * sizeof(int32_t))) != hipSuccess)
-        return c->hip_fail(e, "hipMalloc(finish)");
-      A.need_exact = c->fast_finish ? (int32_t*)((char*)c->fin.p + fbytes) : nullptr;
-      A.exact_list = c->fast_finish ? (int32_t*)((char*)c->fin.p + fbytes + lbytes) : nullptr;
-      if ((e = c->h_fin.ensure(fbytes + (size_t)nw * sizeof(int32_t))) != hipSuccess)
-        return c->hip_fail(e, "hipHostMalloc(finish)");
-      // the exact pass on x_stream (when there is one and the fast pass runs first)
-      hipStream_t fs = (c->x_stream && A.need_exact) ? c->x_stream : c->stream;
-      if ((e = csm::launch_finish(A, (const ScanWork*)c->scans.p, (const AngleEntry*)c->angles.p,
-                                  (const double*)c->scores.p, (csm::FinishOut*)c->fin.p, nw, c->stream, fs,
-                                  c->ev_fast)) != hipSuccess)
-        return c->hip_fail(e, "finish_kernel");
-      if (time_fin && fs != c->stream && (e = hipEventRecord(c->ev_ft, c->stream)) != hipSuccess)
-        return c->hip_fail(e, "hipEventRecord");
-      if (time_fin && (e = hipEventRecord(c->ev2, fs)) != hipSuccess) return c->hip_fail(e, "hipEventRecord");
-      // with profiling on, the flags come back too: how many windows needed the exact sort
-      const size_t cbytes = fbytes + ((time_fin && A.need_exact) ? (size_t)nw * sizeof(int32_t) : 0);
-      if ((e = hipEventRecord(c->ev_k, fs)) != hipSuccess || (e = hipStreamWaitEvent(c->d2h, c->ev_k, 0)) != hipSuccess)
-        return c->hip_fail(e, "kernels event");
-      if ((e = hipMemcpyAsync(c->h_fin.p, c->fin.p, cbytes, hipMemcpyDeviceToHost, c->d2h)) != hipSuccess)
-        return c->hip_fail(e, "hipMemcpyAsync(finish)");
-      if (cbytes > fbytes) {
-        flags_h = (const int32_t*)((const char*)c->h_fin.p + fbytes);
-        n_flags = nw;
-      }
-    }
-  } else {
-    const size_t pbytes = (size_t)nw * (size_t)bps * sizeof(BestPartial);
-    if ((e = c->partials.ensure(pbytes)) != hipSuccess) return c->hip_fail(e, "hipMalloc(partials)");
+  if (best) {
+    if ((e = c->partials.ensure((size_t)nw * (size_t)shape.bps * sizeof(BestPartial))) != hipSuccess)
+      return c->hip_fail(e, "hipMalloc(partials)");
     if ((e = c->best.ensure((size_t)nw * sizeof(BestPartial))) != hipSuccess) return c->hip_fail(e, "hipMalloc(best)");
-    if (box_pair)
-      e = csm::launch_score_box_pair(L, (const ScanWork*)c->scans.p, (const double*)c->pts.p,
-                                     (const AngleEntry*)c->angles.p, nullptr, (BestPartial*)c->partials.p,
-                                     D.n_space, c->stream);
-    else if (box || box_tiled)
-      e = csm::launch_score_box(L, (const ScanWork*)c->scans.p, (const double*)c->pts.p,
-                                (const AngleEntry*)c->angles.p, nullptr, (BestPartial*)c->partials.p,
-                                box_tiled ? 16 : D.n_space, c->stream);
-    else if (phase)
-      e = csm::launch_score_phase(L, PT, (const ScanWork*)c->scans.p, (const double*)c->pts.p,
-                                  (const AngleEntry*)c->angles.p, nullptr, (BestPartial*)c->partials.p,
-                                  D.n_space, c->stream);
-    else if (tiny)
-      e = csm::launch_score_tiny(L, (const ScanWork*)c->scans.p, (const double*)c->pts.p,
-                                 (const AngleEntry*)c->angles.p, nullptr, (BestPartial*)c->partials.p, D.n_space,
-                                 c->stream);
-    else if (rows_sq)
-      e = csm::launch_score_rows(L, (const ScanWork*)c->scans.p, (const double*)c->pts.p,
-                                 (const AngleEntry*)c->angles.p, nullptr, (BestPartial*)c->partials.p,
-                                 D.n_space, rows_sq, c->stream);
-    else
-      e = csm::launch_score_cols(L, (const ScanWork*)c->scans.p, (const double*)c->pts.p,
-                                 (const AngleEntry*)c->angles.p, nullptr, (BestPartial*)c->partials.p,
-                                 kt, c->stream);
-    if (e != hipSuccess) return c->hip_fail(e, "score kernel (best)");
-    if (c->profiling && (e = hipEventRecord(c->ev1, c->stream)) != hipSuccess) return c->hip_fail(e, "hipEventRecord");
-    if (box_tiled) {  // (window, tile) over its angles, then window over its tiles: one
-                      // block per window over ~10^5 partials took 0.13 ms on willow
-      const int32_t tpw = tile_n * tile_n;
-      if ((e = c->best_tiles.ensure((size_t)nw * tpw * sizeof(BestPartial))) != hipSuccess)
-        return c->hip_fail(e, "hipMalloc(tile bests)");
-      if ((e = csm::launch_reduce_best((const BestPartial*)c->partials.p, D.n_angles, nw * tpw,
-                                       (BestPartial*)c->best_tiles.p, c->stream)) != hipSuccess ||
-          (e = csm::launch_reduce_best((const BestPartial*)c->best_tiles.p, tpw, nw, (BestPartial*)c->best.p,
-                                       c->stream)) != hipSuccess)
-        return c->hip_fail(e, "reduce_best_kernel");
-    } else if ((e = csm::launch_reduce_best((const BestPartial*)c->partials.p, (int32_t)bps, nw,
-                                            (BestPartial*)c->best.p, c->stream)) != hipSuccess) {
-      return c->hip_fail(e, "reduce_best_kernel");
-    }
-    if ((e = hipEventRecord(c->ev_k, c->stream)) != hipSuccess || (e = hipStreamWaitEvent(c->d2h, c->ev_k, 0)) != hipSuccess)
-      return c->hip_fail(e, "kernels event");
-    if ((e = hipMemcpyAsync(best_out, c->best.p, (size_t)nw * sizeof(BestPartial), hipMemcpyDeviceToHost, c->d2h)) != hipSuccess)
-      return c->hip_fail(e, "hipMemcpyAsync(best)");
+  } else if ((e = c->scores.ensure((size_t)nw * (size_t)stride * sizeof(double))) != hipSuccess) {
+    return c->hip_fail(e, "hipMalloc(scores)");
   }
-  PendingRun local;
-  PendingRun& p = pend ? *pend : local;
-  p = PendingRun{};
+  if (sp.score &&  // (otherwise scored by earlier calls)
+      (e = launch_score(shape, L, PT, (const ScanWork*)c->scans.p + w0, (const double*)c->pts.p,
+                        (const AngleEntry*)c->angles.p, best ? nullptr : (double*)c->scores.p,
+                        best ? (BestPartial*)c->partials.p : nullptr, c->stream)) != hipSuccess)
+    return c->hip_fail(e, best ? "score kernel (best)" : "score kernel");
+  if (dec.tail && sp.score) c->tail_open = w1 < nw;  // the level's last window is out: its counters close
+  if (sp.score && c->profiling && (e = hipEventRecord(c->ev1, c->stream)) != hipSuccess)
+    return c->hip_fail(e, "hipEventRecord");
+  if (sp.score && !sp.finish && w0 == 0 && c->profiling && (e = hipEventRecord(c->ev_g0, c->stream)) != hipSuccess)
+    return c->hip_fail(e, "hipEventRecord");  // the first span's end
+  return CSM_OK;
+}
+
+// The level's finish, one function per mode. Every score to the host:
+int Launch::finish_scores_to_host() {
+  const size_t bytes = (size_t)nw * (size_t)D.n_cand * sizeof(double);
+  hipError_t e;
+  if ((e = c->h_scores.ensure(bytes)) != hipSuccess) return c->hip_fail(e, "hipHostMalloc(scores)");
+  if ((e = hipEventRecord(c->ev_k, c->stream)) != hipSuccess || (e = hipStreamWaitEvent(c->d2h, c->ev_k, 0)) != hipSuccess)
+    return c->hip_fail(e, "kernels event");
+  if ((e = hipMemcpyAsync(c->h_scores.p, c->scores.p, bytes, hipMemcpyDeviceToHost, c->d2h)) != hipSuccess)
+    return c->hip_fail(e, "hipMemcpyAsync(scores)");
+  return CSM_OK;
+}
+
+// The finish kernels' launch and the events that time them (exact pass on fs).
+int Launch::launch_finish_timed(const csm::FinishArgs& A, csm::FinishOut* out, hipStream_t fs, bool fast_done) {
+  hipError_t e;
+  if ((e = csm::launch_finish(A, (const ScanWork*)c->scans.p, (const AngleEntry*)c->angles.p,
+                              (const double*)c->scores.p, out, nw, c->stream, fs, c->ev_fast, fast_done)) != hipSuccess)
+    return c->hip_fail(e, "finish_kernel");
+  if (time_fin() && fs != c->stream && (e = hipEventRecord(c->ev_ft, c->stream)) != hipSuccess)
+    return c->hip_fail(e, "hipEventRecord");
+  if (time_fin() && (e = hipEventRecord(c->ev2, fs)) != hipSuccess) return c->hip_fail(e, "hipEventRecord");
+  return CSM_OK;
+}
+
+// The signalled finish: with the fused finish the scoring launches did the
+// fast pass's work, and only the exact pass is launched, after them.
+int Launch::finish_signalled() {
+  done_stream = c->x_stream ? c->x_stream : c->stream;
+  return launch_finish_timed(SA, sig_out, done_stream, dec.tail);
+}
+
+// The plain device finish: FinishOut to device memory, then down on d2h.
+int Launch::finish_device() {
+  hipError_t e;
+  csm::FinishArgs A = finish_args(P, D, G, skip_lists);
+  const size_t fbytes = (size_t)nw * sizeof(csm::FinishOut);
+  // + one "needs the exact sort" flag per window (fast finish, csm_finish.hip)
+  // + the flags' compacted list (count, then windows)
+  const size_t lbytes = ((size_t)nw * sizeof(int32_t) + 7) & ~(size_t)7;  // the list's {count, tag}: 8-aligned
+  if ((e = c->fin.ensure(fbytes + lbytes + (size_t)(nw + 2) * sizeof(int32_t))) != hipSuccess)
+    return c->hip_fail(e, "hipMalloc(finish)");
+  A.need_exact = c->fast_finish ? (int32_t*)((char*)c->fin.p + fbytes) : nullptr;
+  A.exact_list = c->fast_finish ? (int32_t*)((char*)c->fin.p + fbytes + lbytes) : nullptr;
+  if ((e = c->h_fin.ensure(fbytes + (size_t)nw * sizeof(int32_t))) != hipSuccess)
+    return c->hip_fail(e, "hipHostMalloc(finish)");
+  // the exact pass on x_stream (when there is one and the fast pass runs first)
+  hipStream_t fs = (c->x_stream && A.need_exact) ? c->x_stream : c->stream;
+  const int st = launch_finish_timed(A, (csm::FinishOut*)c->fin.p, fs, false);
+  if (st != CSM_OK) return st;
+  // with profiling on, the flags come back too: how many windows needed the exact sort
+  const size_t cbytes = fbytes + ((time_fin() && A.need_exact) ? (size_t)nw * sizeof(int32_t) : 0);
+  if ((e = hipEventRecord(c->ev_k, fs)) != hipSuccess || (e = hipStreamWaitEvent(c->d2h, c->ev_k, 0)) != hipSuccess)
+    return c->hip_fail(e, "kernels event");
+  if ((e = hipMemcpyAsync(c->h_fin.p, c->fin.p, cbytes, hipMemcpyDeviceToHost, c->d2h)) != hipSuccess)
+    return c->hip_fail(e, "hipMemcpyAsync(finish)");
+  if (cbytes > fbytes) {
+    flags_h = (const int32_t*)((const char*)c->h_fin.p + fbytes);
+    n_flags = nw;
+  }
+  return CSM_OK;
+}
+
+// Best mode: the partials reduced to one BestPartial per window, down on d2h.
+int Launch::finish_best(BestPartial* best_out) {
+  const BestPartial* parts = (const BestPartial*)c->partials.p;
+  hipError_t e;
+  if (shape.kernel == ScoreKernel::kBoxTiled) {  // (window, tile) over its angles, then window over its tiles: one
+                                                   // block per window over ~10^5 partials took 0.13 ms on willow
+    const int32_t tpw = shape.ktiles * shape.ktiles;
+    if ((e = c->best_tiles.ensure((size_t)nw * tpw * sizeof(BestPartial))) != hipSuccess)
+      return c->hip_fail(e, "hipMalloc(tile bests)");
+    if ((e = csm::launch_reduce_best(parts, D.n_angles, nw * tpw, (BestPartial*)c->best_tiles.p, c->stream)) !=
+            hipSuccess ||
+        (e = csm::launch_reduce_best((const BestPartial*)c->best_tiles.p, tpw, nw, (BestPartial*)c->best.p,
+                                     c->stream)) != hipSuccess)
+      return c->hip_fail(e, "reduce_best_kernel");
+  } else if ((e = csm::launch_reduce_best(parts, (int32_t)shape.bps, nw, (BestPartial*)c->best.p, c->stream)) !=
+             hipSuccess) {
+    return c->hip_fail(e, "reduce_best_kernel");
+  }
+  if ((e = hipEventRecord(c->ev_k, c->stream)) != hipSuccess || (e = hipStreamWaitEvent(c->d2h, c->ev_k, 0)) != hipSuccess)
+    return c->hip_fail(e, "kernels event");
+  if ((e = hipMemcpyAsync(best_out, c->best.p, (size_t)nw * sizeof(BestPartial), hipMemcpyDeviceToHost, c->d2h)) != hipSuccess)
+    return c->hip_fail(e, "hipMemcpyAsync(best)");
+  return CSM_OK;
+}
+
+// What wait_run needs to join the level and account its kernels.
+void Launch::fill_pending(const char* kname, PendingRun& p) {
+  pending_base(c, D, plans, kname, p);
   p.flags = flags_h;
   p.n_flags = n_flags;
-  std::snprintf(p.kname, sizeof(p.kname), "%s", kname);
-  std::snprintf(p.fname, sizeof(p.fname), "finish_kernel<%lld>", (long long)D.n_cand);
-  p.alg_bytes = alg_bytes;
-  p.scorings = scorings;
-  p.finish_bytes = (double)nw * (double)D.n_cand * 8.0;
-  p.device_finish = mode == Finish::kDevice && time_fin;
-  p.timed = c->profiling;
-  p.ev0 = c->ev0;
-  p.ev1 = c->ev1;
+  p.device_finish = mode == Finish::kDevice && time_fin();
   // (with the fused finish the fast interval is empty: the scoring time holds it)
-  p.ev_fast = (time_fin && mode == Finish::kDevice && c->fast_finish && c->x_stream) ? c->ev_ft : nullptr;
+  p.ev_fast = (time_fin() && mode == Finish::kDevice && c->fast_finish && c->x_stream) ? c->ev_ft : nullptr;
   if (c->span_gap) {
     p.gap0 = c->ev_g0;
     p.gap1 = c->ev_g1;
     c->span_gap = false;
   }
-  p.ev2 = c->ev2;
-  p.done = c->ev_done;
   p.fin_host = sig_out;
-  p.host_flag = sig_flag;
-  p.fast_flag = sig_fast;
-  p.flag_value = sig_value;
+  p.host_flag = SA.host_flag;
+  p.fast_flag = SA.host_fast_flag;
+  p.flag_value = SA.flag_value;
   p.defer_timing = sig;
-  if ((e = hipEventRecord(c->ev_done, done_stream)) != hipSuccess) return c->hip_fail(e, "hipEventRecord");
+}
+
+int run_windows(csm_ctx* c, const csm_param& P, const Dims& D, const Geometry& G,
+                const std::vector<WindowPlan>& plans, const std::vector<int64_t>& pt_offsets,
+                const AngleEntry* angles, size_t n_angle_entries,
+                const std::vector<int32_t>& grid_index, BestPartial* best_out,
+                Finish mode, PendingRun* pend, int skip_lists, WinSpan sp) {
+  if (best_out) mode = Finish::kBest;
+  const int nw = (int)plans.size();
+  if (nw == 0) return CSM_OK;
+  const int w0 = sp.w1 < 0 ? 0 : sp.w0, w1 = sp.w1 < 0 ? nw : sp.w1;
+  Launch X{c,  P,  D,  G,  plans, angles, n_angle_entries, mode, skip_lists,
+           sp, nw, w0, w1, w0 == 0 && w1 == nw && sp.score && sp.finish, P.search_space_resolution / G.mres};
+  const double tp0 = c->profiling ? now_ms() : 0.0;  // host cost of the launch before its inputs (host:launch:prep)
+  if (!c->deferred.empty()) {  // the events below are recorded again
+    const int fst = flush_deferred(c);
+    if (fst != CSM_OK) return fst;
+  }
+  const double tp1 = c->profiling ? now_ms() : 0.0;  // (the deferred event reads are profiling's own cost)
+  if (c->profiling) c->account("host:launch:flush_events", (float)(tp1 - tp0), 0.0, 0.0);
+  int st;
+  hipError_t e;
+  // validate and decide
+  if ((st = X.validate()) != CSM_OK) return st;
+  if (X.whole && mode != Finish::kBest && c->int_ok && X.S.in_range && small_launch(c, D, nw))
+    return run_windows_small(c, P, D, G, plans, pt_offsets, angles, n_angle_entries, grid_index,
+                             mode == Finish::kDevice, pend, skip_lists);
+  if ((st = X.decide()) != CSM_OK) return st;
+  // stage: the windows' ScanWork and the LevelWork, the signalled and the fused finish
+  if ((st = X.level_work(pt_offsets, grid_index)) != CSM_OK) return st;
+  if (X.sig && (st = X.stage_signalled()) != CSM_OK) return st;
+  if (X.dec.tail && (st = X.stage_tail()) != CSM_OK) return st;
+  if ((e = c->scans.ensure((size_t)nw * sizeof(ScanWork))) != hipSuccess) return c->hip_fail(e, "hipMalloc(scans)");
+  if ((e = c->angles.ensure(n_angle_entries * sizeof(AngleEntry))) != hipSuccess) return c->hip_fail(e, "hipMalloc(angles)");
+  const double tl0 = c->profiling ? now_ms() : 0.0;  // host cost of the launch, by phase
+  if (c->profiling) c->account("host:launch:prep", (float)(tl0 - tp1), 0.0, 0.0);
+  // send the span's inputs, launch its scoring
+  if (sp.score && (st = X.send_inputs()) != CSM_OK) return st;
+  char kname[48];
+  score_kernel_name(X.shape, kname, sizeof(kname));
+  const double tl1 = c->profiling ? now_ms() : 0.0;
+  if ((st = X.scoring()) != CSM_OK) return st;
+  if (c->profiling && mode != Finish::kBest) {
+    c->account("host:launch:inputs", (float)(tl1 - tl0), 0.0, 0.0);
+    c->account("host:launch:score", (float)(now_ms() - tl1), 0.0, 0.0);
+  }
+  if (!sp.finish) return CSM_OK;  // the finish comes with the level's last call
+  // the level's finish
+  const double tl2 = (c->profiling && mode != Finish::kBest) ? now_ms() : 0.0;
+  X.done_stream = c->d2h;
+  st = mode == Finish::kBest ? X.finish_best(best_out)
+       : mode == Finish::kScoresToHost ? X.finish_scores_to_host()
+       : X.sig ? X.finish_signalled()
+               : X.finish_device();
+  if (st != CSM_OK) return st;
+  PendingRun local;
+  PendingRun& p = pend ? *pend : local;
+  X.fill_pending(kname, p);
+  if ((e = hipEventRecord(c->ev_done, X.done_stream)) != hipSuccess) return c->hip_fail(e, "hipEventRecord");
   if (c->profiling && tl2 > 0.0) c->account("host:launch:finish", (float)(now_ms() - tl2), 0.0, 0.0);
-  if (c->profiling && sig && mode == Finish::kDevice) {  // how the level's fast finish ran (launches: levels; scorings: windows)
+  if (c->profiling && X.sig) {  // how the level's fast finish ran (launches: levels; scorings: windows)
     char nm[48];
-    std::snprintf(nm, sizeof(nm), "finish:%s<%lld>", tail ? "fused" : "separate", (long long)D.n_cand);
+    std::snprintf(nm, sizeof(nm), "finish:%s<%lld>", X.dec.tail ? "fused" : "separate", (long long)D.n_cand);
     c->account(nm, 0.f, 0.0, (double)nw);
   }
-  if (pend) return CSM_OK;
-  return wait_run(c, p);
+  return pend ? CSM_OK : wait_run(c, p);
 }
 
 // Fill a WindowPlan + its AngleEntry rows (AngleSearchLookUpTable::UpdateLookUpTable

@@ -1,7 +1,8 @@
 // csm_level_decision.hpp — what a level's launches decide from its windows,
 // as pure host arithmetic (no HIP, no context): the fixed-point range of a
 // window, the level-wide summary of its beam and point counts, the kernel
-// family and the fused finish chosen from that summary, the spans a level
+// family and the fused finish chosen from that summary, the scoring kernel's
+// shape and stats name that follow from the decision, the spans a level
 // goes out in, and the bound on the next level's windows a split hand-off
 // plans before their poses exist. run_windows, level_begin_split and
 // level_end_begin call these; tests/test_level_decision.py compiles them into
@@ -19,6 +20,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 
 namespace csmh {
 
@@ -156,6 +158,75 @@ inline LevelDecision level_decide(const LevelSummary& S, const LevelCaps& K, int
   d.max_n_used = S.max_n_used;
   d.tail = K.tail_finish && (d.box || d.phase || d.tiny) && S.max_n_used <= kTailMaxBeams && d.use_int;
   return d;
+}
+
+// Which scoring kernel a level's launches run, and in what shape: one value,
+// made once per call from the level's decision, so the stats name, the launch
+// and the finish cannot disagree. In the order of precedence, last first.
+enum class ScoreKernel { kCols, kRows, kBox, kBoxPair, kBoxTiled, kPhase, kTiny };
+
+// What the choice needs from the context and the device code, as plain values.
+struct ShapeFacts {
+  int rows_sq = 0;        // the row-segment kernel's instantiation for this window and step (0: none)
+  bool pair_ok = false;   // the grid's palette and its strip copies are usable (v11)
+  bool tiled_ok = false;  // the box over 16 x 16 tiles is admissible: whole-cell step, padded grid, block count
+  bool best = false;      // best-only mode (the argmax per window, no scores)
+};
+
+struct LaunchShape {
+  ScoreKernel kernel = ScoreKernel::kCols;
+  bool use_int = false, best = false;
+  int n_space = 0;
+  int rows_sq = 0;         // nonzero only for kRows
+  // 16-wide tiles per window edge (the tiled box's; the v2 column kernel's,
+  // with KT rows per lane, balanced so at most a few rows idle)
+  int ktiles = 0, kt = 0;
+  int64_t n_cols = 0, col_blocks = 0;
+  int64_t bps = 0;  // blocks per window
+};
+
+// Precedence: pair box, box, tiled box, phase, tiny, row segments, columns.
+// The tiled box (v6 over 16 x 16 tiles: the argmax of a one-cell-step window
+// wider than 16, loop-closure windows, in place of the column kernel's dword
+// gathers) only in best mode and only when the box is not taken; row segments
+// only when none of the five before them is. The same for every span of a level.
+inline LaunchShape launch_shape(const LevelDecision& d, int n_angles, int n_space, const ShapeFacts& F) {
+  LaunchShape s;
+  s.use_int = d.use_int;
+  s.best = F.best;
+  s.n_space = n_space;
+  s.ktiles = (n_space + 15) / 16;
+  s.kt = (n_space + s.ktiles - 1) / s.ktiles;
+  s.n_cols = (int64_t)n_angles * n_space;
+  s.col_blocks = (s.n_cols + 63) / 64;
+  const bool tiled = !d.box && F.best && d.use_int && d.box_points_ok && F.tiled_ok && n_space > 16;
+  s.kernel = d.box ? (F.pair_ok ? ScoreKernel::kBoxPair : ScoreKernel::kBox)
+             : tiled ? ScoreKernel::kBoxTiled
+             : d.phase ? ScoreKernel::kPhase
+             : d.tiny ? ScoreKernel::kTiny
+             : F.rows_sq && n_space <= 64 ? ScoreKernel::kRows
+                         : ScoreKernel::kCols;
+  s.rows_sq = s.kernel == ScoreKernel::kRows ? F.rows_sq : 0;
+  const int64_t rows_groups = s.rows_sq ? 64 / n_space : 1;
+  s.bps = s.kernel == ScoreKernel::kBoxTiled ? (int64_t)s.ktiles * s.ktiles * n_angles
+          : s.kernel == ScoreKernel::kRows   ? (n_angles + rows_groups - 1) / rows_groups
+          : s.kernel == ScoreKernel::kCols   ? s.col_blocks * s.ktiles
+                                             : n_angles;
+  return s;
+}
+
+// The launch's name in the kernel stats (tests, bench.py and tools/ match on these).
+inline void score_kernel_name(const LaunchShape& s, char* out, size_t n) {
+  const char* m = s.best ? "best" : "all";
+  switch (s.kernel) {
+    case ScoreKernel::kBoxPair: std::snprintf(out, n, "score_box_pair_kernel<%d,%s>", s.n_space, m); break;
+    case ScoreKernel::kBox: std::snprintf(out, n, "score_box_kernel<%d,%s>", s.n_space, m); break;
+    case ScoreKernel::kBoxTiled: std::snprintf(out, n, "score_box_kernel<16,best,tiles>"); break;
+    case ScoreKernel::kPhase: std::snprintf(out, n, "score_phase_kernel<%d,%s>", s.n_space, m); break;
+    case ScoreKernel::kTiny: std::snprintf(out, n, "score_tiny_kernel<%d,%s>", s.n_space, m); break;
+    case ScoreKernel::kRows: std::snprintf(out, n, "score_rowsd_kernel<%d,%d,%s>", s.n_space, s.rows_sq, m); break;
+    case ScoreKernel::kCols: std::snprintf(out, n, "score_cols_kernel<%d,%s,%s>", s.kt, s.use_int ? "int" : "f64", m); break;
+  }
 }
 
 // level_begin_split's spans: the span that starts at w0 with nominal size sz

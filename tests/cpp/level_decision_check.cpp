@@ -8,12 +8,15 @@
 // window-by-window check refuses; and evaluates the rule run_windows had
 // before (maxima over the plans written so far, zeros elsewhere, the range of
 // the call's own span) to show it disagrees on levels with short scans first.
+// Then the scoring kernel's shape and stats name over every combination of
+// their inputs (check_shapes).
 // Stand-alone (tests/test_level_decision.py builds and runs it, once under
 // ASan + UBSan); no HIP, no library.
 #include "csm_level_decision.hpp"
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <utility>
 #include <vector>
 
@@ -96,6 +99,95 @@ std::vector<Call> split_calls(int nw, int first, int growth, int trial) {
 std::vector<Call> handoff_calls(int nw) {
   const int h = nw / 2;
   return {{0, h, h}, {h, nw, nw}, {0, nw, nw}};
+}
+
+// The kernel's shape and its stats name (launch_shape, score_kernel_name)
+// over every combination of the caps, fixed point or not, the box offsets,
+// best or all, pair usable, tiled admissible, a row sq of 0 or 2 and these
+// window widths. The names are the literals tests, bench.py and tools/ match.
+const int kSpace[6] = {3, 11, 13, 16, 21, 65};
+const int kKt[6] = {3, 11, 13, 16, 11, 13}, kTiles[6] = {1, 1, 1, 1, 2, 5};  // ceil(ns / ceil(ns / 16)), ceil(ns / 16)
+#define SIX(p, s) {p "3" s, p "11" s, p "13" s, p "16" s, p "21" s, p "65" s}
+const char* const kPairNames[2][6] = {SIX("score_box_pair_kernel<", ",all>"), SIX("score_box_pair_kernel<", ",best>")};
+const char* const kBoxNames[2][6] = {SIX("score_box_kernel<", ",all>"), SIX("score_box_kernel<", ",best>")};
+const char* const kPhaseNames[2][6] = {SIX("score_phase_kernel<", ",all>"), SIX("score_phase_kernel<", ",best>")};
+const char* const kTinyNames[2][6] = {SIX("score_tiny_kernel<", ",all>"), SIX("score_tiny_kernel<", ",best>")};
+const char* const kRowsNames[2][6] = {SIX("score_rowsd_kernel<", ",2,all>"), SIX("score_rowsd_kernel<", ",2,best>")};
+#undef SIX
+const char* const kColsNames[2][2][6] = {  // [int][best][width]: KT, not the width
+    {{"score_cols_kernel<3,f64,all>", "score_cols_kernel<11,f64,all>", "score_cols_kernel<13,f64,all>",
+      "score_cols_kernel<16,f64,all>", "score_cols_kernel<11,f64,all>", "score_cols_kernel<13,f64,all>"},
+     {"score_cols_kernel<3,f64,best>", "score_cols_kernel<11,f64,best>", "score_cols_kernel<13,f64,best>",
+      "score_cols_kernel<16,f64,best>", "score_cols_kernel<11,f64,best>", "score_cols_kernel<13,f64,best>"}},
+    {{"score_cols_kernel<3,int,all>", "score_cols_kernel<11,int,all>", "score_cols_kernel<13,int,all>",
+      "score_cols_kernel<16,int,all>", "score_cols_kernel<11,int,all>", "score_cols_kernel<13,int,all>"},
+     {"score_cols_kernel<3,int,best>", "score_cols_kernel<11,int,best>", "score_cols_kernel<13,int,best>",
+      "score_cols_kernel<16,int,best>", "score_cols_kernel<11,int,best>", "score_cols_kernel<13,int,best>"}}};
+
+bool same_shape(const LaunchShape& a, const LaunchShape& b) {
+  return a.kernel == b.kernel && a.use_int == b.use_int && a.best == b.best && a.n_space == b.n_space &&
+         a.rows_sq == b.rows_sq && a.kt == b.kt && a.ktiles == b.ktiles && a.n_cols == b.n_cols &&
+         a.col_blocks == b.col_blocks && a.bps == b.bps;
+}
+
+void check_shapes(long& n_shapes, long kernels_seen[7]) {
+  const int nw = 48, na = 21;
+  for (int bits = 0; bits < (1 << 11); ++bits)
+    for (int si = 0; si < 6; ++si) {
+      const int ns = kSpace[si];
+      LevelCaps K;
+      K.int_grid = bits & 1, K.tail_finish = bits & 2, K.box = bits & 4, K.phase = bits & 8, K.tiny = bits & 16;
+      LevelSummary S;
+      S.n_windows = nw, S.max_n_used = 128, S.in_range = bits & 32, S.points_ok = bits & 64;
+      ShapeFacts F;
+      F.best = bits & 128, F.pair_ok = bits & 256, F.tiled_ok = bits & 512, F.rows_sq = (bits & 1024) ? 2 : 0;
+      const LevelDecision d = level_decide(S, K, 0, nw);
+      const LaunchShape s = launch_shape(d, na, ns, F);
+      // exactly one kernel, in the precedence: pair box, box, tiled box, phase, tiny, row segments, columns
+      const bool tiled = !d.box && F.best && d.use_int && d.box_points_ok && F.tiled_ok && ns > 16;
+      const bool rows = !d.box && !tiled && !d.phase && !d.tiny && F.rows_sq && ns <= 64;
+      const ScoreKernel want = d.box && F.pair_ok ? ScoreKernel::kBoxPair
+                               : d.box            ? ScoreKernel::kBox
+                               : tiled            ? ScoreKernel::kBoxTiled
+                               : d.phase          ? ScoreKernel::kPhase
+                               : d.tiny           ? ScoreKernel::kTiny
+                               : rows             ? ScoreKernel::kRows
+                                                  : ScoreKernel::kCols;
+      if (s.kernel != want) fail("the shape's kernel is not the precedence's", bits);
+      if (s.kernel == ScoreKernel::kBoxTiled && !F.best) fail("the tiled box outside best mode", bits);
+      if ((s.rows_sq != 0) != (s.kernel == ScoreKernel::kRows)) fail("rows_sq set for another kernel than the rows'", bits);
+      if (s.kt != kKt[si] || s.ktiles != kTiles[si] || s.n_space != ns) fail("the column tiling", bits);
+      // blocks per window, as run_windows had it
+      const int64_t n_cols = (int64_t)na * ns, col_blocks = (n_cols + 63) / 64;
+      const int64_t groups = s.rows_sq ? 64 / ns : 1;
+      const bool wave_per_angle = s.kernel == ScoreKernel::kBox || s.kernel == ScoreKernel::kBoxPair ||
+                                  s.kernel == ScoreKernel::kPhase || s.kernel == ScoreKernel::kTiny;
+      const int64_t bps = s.kernel == ScoreKernel::kBoxTiled ? (int64_t)kTiles[si] * kTiles[si] * na
+                          : wave_per_angle                   ? na
+                          : s.rows_sq                        ? (na + groups - 1) / groups
+                                                             : col_blocks * kTiles[si];
+      if (s.bps != bps || s.n_cols != n_cols || s.col_blocks != col_blocks) fail("blocks per window", bits);
+      const int b = F.best ? 1 : 0;
+      const char* name = s.kernel == ScoreKernel::kBoxPair    ? kPairNames[b][si]
+                         : s.kernel == ScoreKernel::kBox      ? kBoxNames[b][si]
+                         : s.kernel == ScoreKernel::kBoxTiled ? "score_box_kernel<16,best,tiles>"
+                         : s.kernel == ScoreKernel::kPhase    ? kPhaseNames[b][si]
+                         : s.kernel == ScoreKernel::kTiny     ? kTinyNames[b][si]
+                         : s.kernel == ScoreKernel::kRows     ? kRowsNames[b][si]
+                                                              : kColsNames[d.use_int ? 1 : 0][b][si];
+      char got[48];
+      score_kernel_name(s, got, sizeof(got));
+      if (std::strcmp(got, name) != 0) {
+        std::printf("name %s, expected %s\n", got, name);
+        fail("the kernel's stats name", bits);
+      }
+      // every span of the level, and its finish-only call, gets the same shape
+      const int spans[4][2] = {{0, 5}, {5, nw}, {nw - 1, nw}, {0, nw}};
+      for (const auto& sp : spans)
+        if (!same_shape(launch_shape(level_decide(S, K, sp[0], sp[1]), na, ns, F), s)) fail("a span's shape differs", bits);
+      ++n_shapes;
+      ++kernels_seen[(int)s.kernel];
+    }
 }
 
 }  // namespace
@@ -274,8 +366,13 @@ int main(int argc, char** argv) {
     const LevelDecision pz = parent_decide(L, K, E, L.nw, 0, L.nw);
     std::printf("short_first before: span1_tail=%d finish_tail=%d\n", (int)p0.tail, (int)pz.tail);
   }
-  std::printf("levels=%d calls=%ld one_launch=%ld bounds=%ld parent_disagrees=%ld short_first=%ld short_first_parent_disagrees=%ld\n",
-              trials, n_calls, one_launch, bound_checked, parent_bad_levels, short_first_levels, short_first_parent_bad);
+  long n_shapes = 0, kernels_seen[7] = {0, 0, 0, 0, 0, 0, 0}, kernels_chosen = 0;
+  check_shapes(n_shapes, kernels_seen);
+  for (long k : kernels_seen) kernels_chosen += k > 0;
+  std::printf("levels=%d calls=%ld one_launch=%ld bounds=%ld parent_disagrees=%ld short_first=%ld short_first_parent_disagrees=%ld "
+              "shapes=%ld kernels_chosen=%ld\n",
+              trials, n_calls, one_launch, bound_checked, parent_bad_levels, short_first_levels, short_first_parent_bad,
+              n_shapes, kernels_chosen);
   std::printf("level_decision_check ok\n");
   return 0;
 }

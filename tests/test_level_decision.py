@@ -7,7 +7,11 @@ level_begin_split's spans (first span 1-8 windows, growth 2-4) and as the
 two-span hand-off, and checks that every call of a level decides what the
 one-launch level decides. It also evaluates the rule run_windows had before
 (maxima over the plans written so far) and reports that it disagrees on the
-levels with short scans first: the defect this decision replaced. The same
+levels with short scans first: the defect this decision replaced. Then the
+scoring kernel's shape (launch_shape) and its stats name over every
+combination of their inputs: one kernel in the fixed precedence, the tiled
+box in best mode only, rows_sq for the row kernel only, the blocks per window,
+the names as literals, the same shape for every span of a level. The same
 program once more under ASan + UBSan, stand-alone. No GPU."""
 import os
 import re
@@ -35,6 +39,10 @@ def _check(out):
     f = {k: int(v) for k, v in re.findall(r"(\w+)=(\d+)", out.splitlines()[-2])}
     assert f["levels"] >= 600 and f["calls"] > 3 * f["levels"]
     assert f["one_launch"] > 0 and f["bounds"] > 0
+    # launch_shape and score_kernel_name: 2^11 combinations of the caps, fixed
+    # point, box offsets, best | all, pair, tiled and row sq, at 6 window
+    # widths; every one of the 7 kernels was chosen somewhere
+    assert f["shapes"] == 2048 * 6 and f["kernels_chosen"] == 7
     # the rule before: wrong on every short-first level, and on others
     assert f["short_first"] >= 20
     assert f["short_first_parent_disagrees"] == f["short_first"]
