@@ -91,6 +91,13 @@ const char* csm_frontend_last_error(const csm_frontend* fe);
  * with the scan (used when use_odometry). */
 int csm_frontend_process(csm_frontend* fe, const double* points_xy, int32_t n_points, const double odom_pose[3],
                          csm_frontend_result* result);
+/* One scan as the reference receives it: the LaserScan's n_beams float32
+ * ranges (SlamNode::LaserScanCallback -> BuildRangeDataContainer,
+ * roborts_slam_node.cpp:122,290-311). csm_ranges_to_points with factor 1.0 on
+ * the host (the single-scan path keeps host points for its three maps), then
+ * csm_frontend_process. */
+int csm_frontend_process_ranges(csm_frontend* fe, const csm_laser* laser, const float* ranges,
+                                const double odom_pose[3], csm_frontend_result* result);
 /* Borrow one of the front-end's maps (owned by the front-end; null before the
  * first scan). */
 int csm_frontend_map(csm_frontend* fe, int32_t which, csm_gridmap** map);

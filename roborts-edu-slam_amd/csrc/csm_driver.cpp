@@ -1064,6 +1064,7 @@ int csm_load_scans_async(csm_ctx* c, int32_t n_scans, const double* pts, const i
   S.off.assign(offsets, offsets + n_scans + 1);
   for (auto& o : S.off) o -= offsets[0];
   S.n = n_scans;
+  S.from_ranges = false;
   c->staged_count++;
   return CSM_OK;
 }
@@ -1086,6 +1087,13 @@ int take_staged(csm_ctx* c) {
   hipError_t e;
   if ((e = hipEventSynchronize(S.ready)) != hipSuccess) return c->hip_fail(e, "hipEventSynchronize(stage)");
   std::swap(c->pts, S.pts);
+  if (S.from_ranges) {  // the device's prefix counts, copied down before `ready`
+    const int64_t* oh = (const int64_t*)S.off_h.p;
+    S.off.assign(oh, oh + S.n + 1);
+  }
+  // swapped, never assigned: a pending submitted batch's last launch still
+  // reads the outgoing offsets through its job's pointer (they park in S.off
+  // as its points park in S.pts)
   c->loaded_off.swap(S.off);
   c->loaded_n = S.n;
   c->loaded_grid.clear();

@@ -73,6 +73,7 @@ struct csm_frontend {
   double scan_match_score = 0.0;
   int map_penalize_times = 0;
   std::vector<double> pub_pts, coarse_pts, fine_pts;
+  std::vector<double> range_pts;  // csm_frontend_process_ranges: the scan's endpoints (m)
   // the kept scans (SensorDataManager's multiresolution range data,
   // slam_processor.cpp:216-221): sensor-frame points (m), the pose each was
   // drawn at (:196-205); CorrectPoseAndMap rebuilds the maps from them
@@ -291,6 +292,18 @@ int csm_frontend_process(csm_frontend* f, const double* pts, int32_t n, const do
   r->score = f->scan_match_score;
   r->map_updated = updated ? 1 : 0;
   return CSM_OK;
+}
+
+int csm_frontend_process_ranges(csm_frontend* f, const csm_laser* laser, const float* ranges, const double odom[3],
+                                csm_frontend_result* r) {
+  if (!f || !r || !odom) return CSM_ERR_INVALID_ARG;
+  if (!laser || !ranges || laser->n_beams <= 0) return f->fail(CSM_ERR_INVALID_ARG, "bad laser or null ranges");
+  // BuildRangeDataContainer (roborts_slam_node.cpp:290-311): metres, factor 1
+  f->range_pts.resize((size_t)laser->n_beams * 2);
+  int64_t off[2] = {0, 0};
+  const int st = csm_ranges_to_points(laser, 1, ranges, 1.0, f->range_pts.data(), laser->n_beams, off);
+  if (st != CSM_OK) return f->fail(st, "csm_ranges_to_points: bad laser (range_min >= range_max or a field not finite)");
+  return csm_frontend_process(f, f->range_pts.data(), (int32_t)off[1], odom, r);
 }
 
 int csm_frontend_matcher(csm_frontend* f, csm_ctx** ctx) {

@@ -564,10 +564,24 @@ struct csm_ctx {
     int32_t n = -1;
     hipEvent_t ready = nullptr;
     unsigned long long* maxabs_h = nullptr;  // pinned
+    // a batch queued as raw ranges (csm_load_ranges*): the ranges as uploaded,
+    // the kept beams per scan, their prefix sums, and those copied to pinned
+    // memory before `ready` (take_staged reads them where it reads maxabs_h)
+    csmh::DevBuf ranges, counts, off_dev;
+    csmh::HostBuf off_h;
+    bool from_ranges = false;
   };
   hipStream_t stage_stream = nullptr;
   Staged staged[2];
   int staged_head = 0, staged_count = 0;
+  // The laser's per-beam (cos a_i, sin a_i) on the device (csm_ranges.cpp),
+  // keyed on (n_beams, angle_min bits, angle_increment bits): uploaded once
+  // per key on stage_stream, ready only once the copy was enqueued and the
+  // stream drained (as trig_tab)
+  csmh::DevBuf laser_tab;
+  bool laser_tab_ready = false;
+  int32_t laser_tab_beams = 0;
+  uint32_t laser_tab_amin = 0, laser_tab_ainc = 0;
 
   // scans made resident by csm_load_scans (offsets relative to pts)
   int32_t loaded_n = -1;
@@ -820,6 +834,7 @@ inline bool map_ready(const csm_ctx* c) { return c->has_grid && c->info.update_i
 int pipe_drain(csm_ctx* c);
 void pipe_free(csm_ctx* c);
 int take_staged(csm_ctx* c);
+int drop_staged(csm_ctx* c);
 int matchers_loaded_locked(csm_ctx* c, const csm_param levels[3], int32_t use_fine, double* poses, double* covs,
                            double* scores);
 

@@ -325,6 +325,18 @@ int64_t pal_scratch_ints(int64_t n);
 // max over n points (x, y) of |x| + |y| (NaN if any is NaN) as the bits of a
 // non-negative double, max-ed into *out (zeroed by the caller)
 hipError_t launch_points_maxabs(const double* pts, int64_t n, unsigned long long* out, hipStream_t stream);
+// Raw laser ranges to endpoints (csm_ranges.hip): the kept beams (range_min <
+// r < threshold) of each of n_scans scans of n_beams ranges counted, the
+// counts' prefix sums (n_scans + 1 int64) and the kept beams' points
+// ((cos a_i * r) * factor, (sin a_i * r) * factor; cos_sin: n_beams pairs)
+// written in beam order at offsets[s]. pts holds offsets[n_scans] points, at
+// most n_scans * n_beams.
+hipError_t launch_ranges_count(const float* ranges, int32_t n_scans, int32_t n_beams, double range_min,
+                               double threshold, int32_t* counts, hipStream_t stream);
+hipError_t launch_ranges_offsets(const int32_t* counts, int32_t n_scans, int64_t* offsets, hipStream_t stream);
+hipError_t launch_ranges_points(const float* ranges, int32_t n_scans, int32_t n_beams, double range_min,
+                                double threshold, double factor, const double* cos_sin, const int64_t* offsets,
+                                double* pts, hipStream_t stream);
 hipError_t launch_build_palette(const int32_t* gridi, int64_t n, int32_t* scratch, int32_t* vals, int32_t* state,
                                 uint8_t* idx, hipStream_t stream);
 // v11 pair box kernel: palettes of at most kPairMaxPal values, read from

@@ -29,6 +29,8 @@ EXPORTED = (
     "csm_scan_match_batch", "csm_scan_matchers_batch", "csm_score_window",
     "csm_best_window", "csm_load_scans", "csm_scan_matchers_loaded", "csm_scan_matchers_submit", "csm_scan_matchers_wait", "csm_load_scans_async",
     "csm_host_alloc", "csm_host_free",
+    "csm_laser_range_threshold", "csm_ranges_to_points", "csm_load_ranges", "csm_load_ranges_async",
+    "csm_loaded_scans",
     "csm_set_profiling", "csm_kernel_stats", "csm_sort_order", "csm_phase_buckets",
     "csm_set_grid_stack", "csm_best_windows", "csm_optimize_scan_match", "csm_optimize_scan_match_batch",
     "csm_optimize_update_cost", "csm_load_scans_grids", "csm_scan_matchers_batch_grids",
@@ -42,7 +44,7 @@ EXPORTED = (
     # include/csm_frontend.h
     "csm_frontend_create", "csm_frontend_destroy", "csm_frontend_last_error", "csm_frontend_process",
     "csm_frontend_map", "csm_frontend_correct_pose_and_map", "csm_frontend_kept_scans", "csm_frontend_matcher",
-    "csm_frontend_last_phases",
+    "csm_frontend_last_phases", "csm_frontend_process_ranges",
     # include/csm_loop_closure.h
     "csm_loop_closure_create", "csm_loop_closure_destroy", "csm_loop_closure_last_error",
     "csm_loop_closure_set_submaps", "csm_loop_closure_match",
@@ -78,6 +80,20 @@ class CsmMapInfo(C.Structure):
         ("size_x", C.c_int32),
         ("size_y", C.c_int32),
         ("update_index", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class CsmLaser(C.Structure):
+    """csm_laser: the sensor_msgs/LaserScan fields BuildRangeDataContainer reads
+    (roborts_slam_node.cpp:290-311) + ParamConfig's range_threshold_scale."""
+    _fields_ = [
+        ("angle_min", C.c_float),
+        ("angle_increment", C.c_float),
+        ("range_min", C.c_float),
+        ("range_max", C.c_float),
+        ("range_threshold_scale", C.c_double),
+        ("n_beams", C.c_int32),
         ("reserved", C.c_int32),
     ]
 
@@ -202,6 +218,7 @@ class CsmGridmapState(C.Structure):
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
 _i32p = C.POINTER(C.c_int32)
+_f32p = C.POINTER(C.c_float)
 _ctx = C.c_void_p
 
 
@@ -231,6 +248,11 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "csm_load_scans_async": (C.c_int, [_ctx, C.c_int32, _dp, _i64p]),
         "csm_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
         "csm_host_free": (C.c_int, [C.c_void_p]),
+        "csm_laser_range_threshold": (C.c_int, [C.POINTER(CsmLaser), _dp]),
+        "csm_ranges_to_points": (C.c_int, [C.POINTER(CsmLaser), C.c_int32, _f32p, C.c_double, _dp, C.c_int64, _i64p]),
+        "csm_load_ranges": (C.c_int, [_ctx, C.POINTER(CsmLaser), C.c_int32, _f32p, C.c_double]),
+        "csm_load_ranges_async": (C.c_int, [_ctx, C.POINTER(CsmLaser), C.c_int32, _f32p, C.c_double]),
+        "csm_loaded_scans": (C.c_int, [_ctx, _i32p, _i64p, C.c_int64, _dp, C.c_int64]),
         "csm_scan_matchers_loaded": (C.c_int, [_ctx, C.POINTER(CsmParam), C.c_int32, _dp, _dp, _dp]),
         "csm_scan_matchers_submit": (C.c_int, [_ctx, C.POINTER(CsmParam), C.c_int32, _dp, _dp, _dp]),
         "csm_scan_matchers_wait": (C.c_int, [C.c_void_p]),
@@ -274,6 +296,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "csm_frontend_destroy": (C.c_int, [C.c_void_p]),
         "csm_frontend_last_error": (C.c_char_p, [C.c_void_p]),
         "csm_frontend_process": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp, C.c_void_p]),
+        "csm_frontend_process_ranges": (C.c_int, [C.c_void_p, C.POINTER(CsmLaser), _f32p, _dp, C.c_void_p]),
         "csm_frontend_map": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
         "csm_frontend_matcher": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
         "csm_frontend_last_phases": (C.c_int, [C.c_void_p, _dp]),

@@ -158,6 +158,22 @@ class SlamFrontEnd:
             raise RuntimeError(f"csm_frontend_process: status {st}: {_lib.csm_frontend_last_error(self._h).decode()}")
         return FrontEndResult.from_c(r)
 
+    def process_ranges(self, laser, ranges, odom_pose) -> FrontEndResult:
+        """csm_frontend_process_ranges: one scan as the LaserScan's float32
+        ranges (laser: a worlds.LaserSpec or an _abi.CsmLaser)."""
+        L = laser if isinstance(laser, _abi.CsmLaser) else laser.to_c()
+        rg = np.ascontiguousarray(ranges, dtype=np.float32).ravel()
+        if rg.size != L.n_beams:
+            raise ValueError(f"{rg.size} ranges for a laser of {L.n_beams} beams")
+        od = np.ascontiguousarray(odom_pose, dtype=np.float64)
+        r = CsmFrontendResult()
+        st = _lib.csm_frontend_process_ranges(self._h, C.byref(L), rg.ctypes.data_as(C.POINTER(C.c_float)),
+                                              od.ctypes.data_as(C.POINTER(C.c_double)), C.byref(r))
+        if st != _abi.CSM_OK:
+            raise RuntimeError(f"csm_frontend_process_ranges: status {st}: "
+                               f"{_lib.csm_frontend_last_error(self._h).decode()}")
+        return FrontEndResult.from_c(r)
+
     def last_phases(self) -> dict:
         """Host wall time (ms) of the last process() call's phases
         (csm_frontend_last_phases): prepare, match, map_check, update_map and

@@ -159,6 +159,14 @@ class LaserSpec:
     def range_threshold(self) -> float:  # sensor_data_manager.h:43-48
         return self.range_min + self.range_threshold_scale * (self.range_max - self.range_min)
 
+    def to_c(self):
+        """The csm_laser of this sensor (include/csm.h): angle_min,
+        angle_increment, range_min and range_max as the float32 fields a
+        sensor_msgs/LaserScan carries them in."""
+        from ._abi import CsmLaser
+        return CsmLaser(float(self.angle_min), float(self.angle_increment), float(np.float32(self.range_min)),
+                        float(np.float32(self.range_max)), float(self.range_threshold_scale), int(self.n_beams), 0)
+
 
 def _edt(wall: np.ndarray) -> np.ndarray:
     from scipy.ndimage import distance_transform_edt
