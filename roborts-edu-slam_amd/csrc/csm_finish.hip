@@ -535,7 +535,7 @@ __device__ __forceinline__ void finish_window(const FinishArgs& A, const ScanWor
 
   const double* sc = scores + (int64_t)w * (A.score_stride ? A.score_stride : A.n_cand);
   // Load, and the limits of the partial sort: max, NaN, and the FindBest
-  // prefix size (every element with DoubleEqual(s, max, 1e-2): the prefix is
+  // prefix size (every element in_response_band(s, max): the prefix is
   // exactly that set, in sorted order).
   double lmax = -INFINITY;
   bool lnan = false;
@@ -558,10 +558,7 @@ __device__ __forceinline__ void finish_window(const FinishArgs& A, const ScanWor
   if (__ballot(lnan) != 0 && lane == 0) atomicOr(&sh->nan, 1);
   {
     int c = 0;
-    for (int i = threadIdx.x; i < n; i += 64 * kWaves) {
-      const double d = keys[i] - lmax;
-      c += (d < 0.0 ? d >= -1e-2 : d <= 1e-2) ? 1 : 0;
-    }
+    for (int i = threadIdx.x; i < n; i += 64 * kWaves) c += in_response_band(keys[i], lmax) ? 1 : 0;
     c = wave_sum_i(c);
     if (lane == 0) atomicAdd(&sh->cnt_a, c);
   }
@@ -679,9 +676,7 @@ __device__ __forceinline__ void finish_window(const FinishArgs& A, const ScanWor
   const ScanWork S = scans[w];
   const int ns = A.n_space;
   const int nss = ns * ns;
-  const double f = A.step_cells;
-  auto cx = [&](int idx) { return S.x0 + ((idx / ns) % ns) * f; };
-  auto cy = [&](int idx) { return S.y0 + (idx % ns) * f; };
+  const CandGrid g{S.x0, S.y0, A.step_cells, ns};
   const double best = keys[0];
   FinishOut* o = reinterpret_cast<FinishOut*>(smem + Lo.fout);  // stored sealed at the end (emit_sealed)
   // The window's angle rows (cos, sin) in LDS for FindBest's sequential sums:
@@ -698,54 +693,20 @@ __device__ __forceinline__ void finish_window(const FinishArgs& A, const ScanWor
     }
   __syncthreads();
   if (threadIdx.x == 0) {
-    // FindBestCandidate (:670-710): sequential sums over the tied prefix.
-    double ax = 0.0, ay = 0.0, thx = 0.0, thy = 0.0, ssum = 0.0;
-    int count = 0;
-    for (int i = 0; i < n; ++i) {
-      const double s = keys[i];
-      const double d = s - best;
-      const bool eq = d < 0.0 ? d >= -1e-2 : d <= 1e-2;  // DoubleEqual(s, best, 1e-2)
-      if (!eq) break;
-      const int idx = vals[i];
-      const int a = idx / nss;
+    auto cos_sin = [&](int a) {
       const AngleEntry ae = staged ? AngleEntry{0.0, acs[a].x, acs[a].y} : angles[S.angle_off + a];
-      ax += cx(idx) * s;
-      ay += cy(idx) * s;
-      thx += ae.cosine * s;
-      thy += ae.sine * s;
-      ssum += s;
-      count++;
-    }
-    const int fi = vals[0];
-    o->front_idx = fi;
-    o->count = count;
-    o->best_score = best;
-    o->thx = thx;
-    o->thy = thy;
-    o->ssum = ssum;
-    if (count > 1) {  // :700-707 (atan2 of thy/ssum, thx/ssum is left to the host)
-      sh->bx = ax / ssum;
-      sh->by = ay / ssum;
-    } else {
-      sh->bx = cx(fi);
-      sh->by = cy(fi);
-    }
-    o->best_x = sh->bx;
-    o->best_y = sh->by;
+      return CosSin{ae.cosine, ae.sine};
+    };
+    find_best(keys, vals, n, best, g, cos_sin, o, &sh->bx, &sh->by);
   }
   __syncthreads();
   CSM_STAMP(4);
   const double bx = sh->bx, by = sh->by;
-  const double lo = best - 0.1;
-  const double bound = (0.5 < lo) ? 0.5 : lo;  // std::min(best - 0.1, 0.5) (:912,:986)
+  const double bound = cov_bound(best);
   const double tol = A.lin_tol;
-  auto near_best = [&](int idx) {
-    const double dx = cx(idx) - bx, dy = cy(idx) - by;
-    const bool ex = dx < 0.0 ? dx >= -fabs(tol) : dx <= fabs(tol);
-    const bool ey = dy < 0.0 ? dy >= -fabs(tol) : dy <= fabs(tol);
-    return ex && ey;
-  };
-  const bool want_pos = !(A.skip_lists & 1), want_ang = !(A.skip_lists & 2);
+  auto near_best = [&](int idx) { return csm::near_best(g.x(idx), g.y(idx), bx, by, tol); };
+  const WantLists want = want_lists(A.skip_lists);
+  const bool want_pos = want.pos, want_ang = want.ang;
   // Stage 2: the angular list reads the sorted order of every element with
   // score >= bound while it still needs near-best ones: all of them when at
   // most 20 are near the best, else up to the 20th near one in sorted order,
@@ -852,7 +813,7 @@ __device__ __forceinline__ void finish_window(const FinishArgs& A, const ScanWor
   // the LDS FinishOut (thread 0's header, the lanes' list entries) to memory, sealed
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  emit_sealed(A, o, out + w, (want_pos ? 1 : 0) | (want_ang ? 2 : 0), kSealExact, lane);
+  emit_sealed(A, o, out + w, want.lists, kSealExact, lane);
   CSM_STAMP(6);
 }
 
@@ -929,15 +890,7 @@ __global__ __launch_bounds__(64 * kWaves) void finish_kernel(FinishArgs A, const
 #endif
 constexpr int kFastCap = 512;      // compacted candidates of step 2
 constexpr int kFastNearCap = 512;  // compacted near-best candidates of step 3
-constexpr int kFastLevels = 8;     // thresholds best - {0.01, 0.02, ..., 0.64}, then everything > bound
 constexpr int kFastAngles = 256;   // angle rows staged in LDS (more: read from memory)
-__device__ __forceinline__ double wave_max_d(double v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const double t = __shfl_xor(v, o, 64);
-    v = (t > v) ? t : v;
-  }
-  return v;
-}
 
 // Host signal (A.host_flag): every block's FinishOut stores complete (write-
 // through sc0 sc1 stores to the coherent host buffer, each wave waits for
@@ -1028,7 +981,7 @@ __device__ __forceinline__ void finish_fast_body(const FinishArgs& A, const Scan
   __shared__ int ni[NCAP];
   __shared__ double acs[ACAP], asn[ACAP];
   __shared__ double red[NW];
-  __shared__ int cnt_s[kFastLevels];
+  __shared__ int cnt_s[kFinishLevels];
   __shared__ int nC_s, nN_s, flag_s;
   __shared__ double sbx, sby;
   // FinishOut is assembled in LDS and stored once at the end (34 16-byte
@@ -1066,7 +1019,7 @@ __device__ __forceinline__ void finish_fast_body(const FinishArgs& A, const Scan
       asn[t] = ae.sine;
     }
   }
-  if (tid < kFastLevels) cnt_s[tid] = 0;
+  if (tid < kFinishLevels) cnt_s[tid] = 0;
   if (tid == 0) {
     nC_s = 0;
     nN_s = 0;
@@ -1081,7 +1034,7 @@ __device__ __forceinline__ void finish_fast_body(const FinishArgs& A, const Scan
     nan |= (v[k] != v[k]);
     m = (v[k] > m) ? v[k] : m;
   }
-  m = wave_max_d(m);
+  m = wave_max(m);
   if (lane == 0) red[wave] = m;
   if (__ballot(nan) != 0 && lane == 0) flag_s = 1;
   __syncthreads();
@@ -1093,60 +1046,38 @@ __device__ __forceinline__ void finish_fast_body(const FinishArgs& A, const Scan
     if (tid == 0) flag();
     return;
   }
-  const double lo = best - 0.1;
-  const double bound = (0.5 < lo) ? 0.5 : lo;  // std::min(best - 0.1, 0.5) (:912,:986)
-  // level k < 7: s > bound and s - best >= -0.01 * 2^k; level 7: s > bound
-  // smallest level holding s (kFastLevels: none), branch-free: d >= -dl holds
-  // from the first level on (dl doubles), so the level counts the failures
-  auto level_of = [&](double s) {
-    const double d = s - best;
-    double dl = 0.01;
-    int lv = 0;
-#pragma unroll
-    for (int k = 0; k < kFastLevels - 1; ++k, dl *= 2.0) lv += (d < -dl) ? 1 : 0;
-    return (s > bound) ? lv : kFastLevels;
-  };
+  const double bound = cov_bound(best);
   int lv[V];
   {
-    // per-lane counts packed 16 bits a level (levels 0-3 in c0, 4-7 in c1; a
-    // wave counts at most 64 * V < 2^16 per level), added across the wave in
-    // two 64-bit words: vector work only. (Per-level ballots and scalar
-    // popcounts kept the CU's one scalar unit busy for every wave: ~4.6 us
-    // of a coarse window's block, tools/fast_blocks.py.)
+    // per-lane counts (LevelCounts; a wave counts at most 64 * V < 2^16 per
+    // level), added across the wave in two 64-bit words: vector work only.
+    // (Per-level ballots and scalar popcounts kept the CU's one scalar unit
+    // busy for every wave: ~4.6 us of a coarse window's block,
+    // tools/fast_blocks.py.)
     static_assert(64 * V < 65536, "16-bit level counts");
-    uint64_t c0 = 0, c1 = 0;
+    LevelCounts lc;
 #pragma unroll
     for (int k = 0; k < V; ++k) {
-      lv[k] = level_of(v[k]);  // -INFINITY padding: no level
-      const uint64_t one = 1ull << (16 * (lv[k] & 3));
-      c0 += lv[k] < 4 ? one : 0ull;
-      c1 += (lv[k] >= 4 && lv[k] < kFastLevels) ? one : 0ull;
+      lv[k] = level_of(v[k], best, bound);  // -INFINITY padding: no level
+      lc.add(lv[k]);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-      c0 += __shfl_xor(c0, o, 64);
-      c1 += __shfl_xor(c1, o, 64);
+      lc.c0 += __shfl_xor(lc.c0, o, 64);
+      lc.c1 += __shfl_xor(lc.c1, o, 64);
     }
-    if (lane < kFastLevels) {
-      const int t = (int)(((lane < 4 ? c0 : c1) >> (16 * (lane & 3))) & 0xFFFF);
+    if (lane < kFinishLevels) {
+      const int t = lc.level(lane);
       if (t) atomicAdd(&cnt_s[lane], t);
     }
   }
   __syncthreads();
   CSM_TS_MAX(19);  // level counts
-  // 2. the smallest level whose cumulative count reaches 20 (or all > bound);
-  // without the positional list, level 0 (exactly FindBest's prefix set)
-  const bool want_pos = !(A.skip_lists & 1), want_ang = !(A.skip_lists & 2);
-  int L = want_pos ? kFastLevels - 1 : 0, cum = 0;
-  for (int k = 0; want_pos && k < kFastLevels; ++k) {
-    cum += cnt_s[k];
-    if (cum >= kCovPoints) {
-      L = k;
-      break;
-    }
-  }
-  int nC = 0;
-  for (int k = 0; k <= L; ++k) nC += cnt_s[k];
+  // 2. the level select_level picks, its scores compacted
+  const WantLists want = want_lists(A.skip_lists);
+  const bool want_pos = want.pos, want_ang = want.ang;
+  int L, nC;
+  select_level(cnt_s, want_pos, &L, &nC);
   if (nC > CAP) {
     if (tid == 0) flag();
     return;
@@ -1161,7 +1092,7 @@ __device__ __forceinline__ void finish_fast_body(const FinishArgs& A, const Scan
       if (lane == 0) base = atomicAdd(&nC_s, popc(mm));
       base = uni(base);
       if (in) {
-        const int p = base + popc(mm & below_mask(lane));
+        const int p = ballot_slot(base, mm, lane);
         ck[p] = v[k];
         ci[p] = i;
       }
@@ -1174,16 +1105,9 @@ __device__ __forceinline__ void finish_fast_body(const FinishArgs& A, const Scan
   // (ck padded with -inf to a multiple of 4: read 4 at a time, 2 LDS loads)
   for (int t = tid; t < nC; t += T) {
     const double x = ck[t];
-    int r = 0, eq = 0;
-    for (int j = 0; j < nC; j += 4) {
-      const double2 u01 = *reinterpret_cast<const double2*>(&ck[j]);
-      const double2 u23 = *reinterpret_cast<const double2*>(&ck[j + 2]);
-      r += ((u01.x > x) ? 1 : 0) + ((u01.y > x) ? 1 : 0) + ((u23.x > x) ? 1 : 0) + ((u23.y > x) ? 1 : 0);
-      eq += ((u01.x == x) ? 1 : 0) + ((u01.y == x) ? 1 : 0) + ((u23.x == x) ? 1 : 0) + ((u23.y == x) ? 1 : 0);
-    }
-    const double d = x - best;
-    const bool inF = d < 0.0 ? d >= -1e-2 : d <= 1e-2;  // DoubleEqual(s, best, 1e-2)
-    if (eq > 1 && (inF || (want_pos && r <= kCovPoints))) flag_s = 1;
+    int r, eq;
+    rank_among(ck, nC, x, &r, &eq);
+    if (tie_matters_positional(eq, r, in_response_band(x, best), want_pos)) flag_s = 1;
     sk[r] = x;  // distinct ranks whenever nothing is flagged
     si[r] = ci[t];
   }
@@ -1193,52 +1117,21 @@ __device__ __forceinline__ void finish_fast_body(const FinishArgs& A, const Scan
     if (tid == 0) flag();
     return;
   }
-  const double f = A.step_cells;
-  auto cx = [&](int idx) { return S.x0 + ((idx / ns) % ns) * f; };
-  auto cy = [&](int idx) { return S.y0 + (idx % ns) * f; };
+  const CandGrid g{S.x0, S.y0, A.step_cells, ns};
   FinishOut* const o = &so;
   // Only the pieces the host reads are stored: the header, plus the lists the
   // level keeps (skip_lists) -- 64 B per window instead of 544 B on a level
   // whose lists are dead, the bytes that cross to host memory with a host signal.
-  const int lists = (want_pos ? 1 : 0) | (want_ang ? 2 : 0);
   auto emit = [&]() {  // all threads: the LDS FinishOut and its seal to out[w]
     __syncthreads();
-    if (wave == 0) emit_sealed(A, &so, out + w, lists, kSealFast, lane);
+    if (wave == 0) emit_sealed(A, &so, out + w, want.lists, kSealFast, lane);
   };
-  if (tid == 0) {  // :676-707, the same sequential sums as finish_kernel
-    double ax = 0.0, ay = 0.0, thx = 0.0, thy = 0.0, ssum = 0.0;
-    int count = 0;
-    for (int r = 0; r < nC; ++r) {
-      const double s = sk[r];
-      const double d = s - best;
-      if (!(d < 0.0 ? d >= -1e-2 : d <= 1e-2)) break;
-      const int idx = si[r];
-      const int a = idx / nss;
-      const double ca = a < ACAP ? acs[a] : angles[S.angle_off + a].cosine;
-      const double sa = a < ACAP ? asn[a] : angles[S.angle_off + a].sine;
-      ax += cx(idx) * s;
-      ay += cy(idx) * s;
-      thx += ca * s;
-      thy += sa * s;
-      ssum += s;
-      count++;
-    }
-    const int fi0 = si[0];
-    o->front_idx = fi0;
-    o->count = count;
-    o->best_score = best;
-    o->thx = thx;
-    o->thy = thy;
-    o->ssum = ssum;
-    if (count > 1) {
-      sbx = ax / ssum;
-      sby = ay / ssum;
-    } else {
-      sbx = cx(fi0);
-      sby = cy(fi0);
-    }
-    o->best_x = sbx;
-    o->best_y = sby;
+  if (tid == 0) {
+    auto cos_sin = [&](int a) {  // the staged rows, memory past them
+      return CosSin{a < ACAP ? acs[a] : angles[S.angle_off + a].cosine,
+                    a < ACAP ? asn[a] : angles[S.angle_off + a].sine};
+    };
+    find_best(sk, si, nC, best, g, cos_sin, o, &sbx, &sby);
     o->n_pos = want_pos ? min(nC, kCovPoints) : 0;
   }
   // positional list (:915-928): the sorted prefix with score > bound, <= 20
@@ -1261,19 +1154,14 @@ __device__ __forceinline__ void finish_fast_body(const FinishArgs& A, const Scan
     const int i = tid + k * T;
     const double s = v[k];
     bool in = false;
-    if (s >= bound) {  // padding (-inf) never qualifies
-      const double dx = cx(i) - bx, dy = cy(i) - by;
-      const bool ex = dx < 0.0 ? dx >= -fabs(tol) : dx <= fabs(tol);
-      const bool ey = dy < 0.0 ? dy >= -fabs(tol) : dy <= fabs(tol);
-      in = ex && ey;
-    }
+    if (s >= bound) in = near_best(g.x(i), g.y(i), bx, by, tol);  // padding (-inf) never qualifies
     const uint64_t mm = __ballot(in);
     if (mm) {
       int base = 0;
       if (lane == 0) base = atomicAdd(&nN_s, popc(mm));
       base = uni(base);
       if (in) {
-        const int p = base + popc(mm & below_mask(lane));
+        const int p = ballot_slot(base, mm, lane);
         if (p < NCAP) {
           nk[p] = s;
           ni[p] = i;
@@ -1292,14 +1180,9 @@ __device__ __forceinline__ void finish_fast_body(const FinishArgs& A, const Scan
   __syncthreads();
   for (int t = tid; t < nN; t += T) {
     const double x = nk[t];
-    int r = 0, eq = 0;
-    for (int j = 0; j < nN; j += 4) {  // (nk padded with -inf like ck)
-      const double2 u01 = *reinterpret_cast<const double2*>(&nk[j]);
-      const double2 u23 = *reinterpret_cast<const double2*>(&nk[j + 2]);
-      r += ((u01.x > x) ? 1 : 0) + ((u01.y > x) ? 1 : 0) + ((u23.x > x) ? 1 : 0) + ((u23.y > x) ? 1 : 0);
-      eq += ((u01.x == x) ? 1 : 0) + ((u01.y == x) ? 1 : 0) + ((u23.x == x) ? 1 : 0) + ((u23.y == x) ? 1 : 0);
-    }
-    if (eq > 1 && r <= kCovPoints) flag_s = 1;
+    int r, eq;
+    rank_among(nk, nN, x, &r, &eq);  // (nk padded with -inf like ck)
+    if (tie_matters_angular(eq, r)) flag_s = 1;
     if (r < kCovPoints) {
       o->ang_idx[r] = ni[t];
       o->ang_score[r] = x;

@@ -21,6 +21,7 @@
 
 #include "csm.h"
 #include "csm_internal.hpp"
+#include "csm_finish_rules.hpp"
 #include "csm_gridmap.h"
 #include "csm_gridmap_internal.hpp"
 #include "host_math.hpp"
@@ -53,7 +54,6 @@ struct csm_ctx;
 namespace csmh {
 constexpr double kMaxVariance = 500.0;      // util/slam_util.h:57
 constexpr double kDoubleTolerance = 1e-06;  // util/slam_util.h:59
-constexpr double kResponseFilterTolerance = 1e-2;  // correlate_scan_matcher.h:763
 constexpr int kMaxVarianceUsePointSize = 20;       // correlate_scan_matcher.h:1033
 
 inline bool double_equal(double a, double b, double tol = kDoubleTolerance) {
@@ -167,8 +167,10 @@ struct CandGeom {
   const AngleEntry* angles;
   double f;
   int64_t ns, nss;
-  double x(int64_t idx) const { return W.x0 + (int)((idx / ns) % ns) * f; }
-  double y(int64_t idx) const { return W.y0 + (int)(idx % ns) * f; }
+  // (x, y) are the finish rules' (csm_finish_rules.hpp; window indices fit an int)
+  csm::CandGrid grid() const { return csm::CandGrid{W.x0, W.y0, f, (int)ns}; }
+  double x(int64_t idx) const { return grid().x((int)idx); }
+  double y(int64_t idx) const { return grid().y((int)idx); }
   const AngleEntry& a(int64_t idx) const { return angles[idx / nss]; }
 };
 

@@ -19,28 +19,20 @@ void host_sort_finish(const double* scores, const Dims& D, const CandGeom& C, co
   for (int64_t i = 0; i < n; ++i) e[(size_t)i] = Entry{scores[i], i};
   std::sort(e.begin(), e.end(), [](const Entry& a, const Entry& b) { return a.score > b.score; });
   const double best = e[0].score;
-  // FindBestCandidate (:670-710)
-  double ax = 0.0, ay = 0.0, thx = 0.0, thy = 0.0, ssum = 0.0;
-  int count = 0;
-  for (size_t i = 0; i < e.size(); ++i) {
-    const double sc = e[i].score;
-    if (!double_equal(sc, best, kResponseFilterTolerance)) break;
-    ax += C.x(e[i].idx) * sc;
-    ay += C.y(e[i].idx) * sc;
-    thx += C.a(e[i].idx).cosine * sc;  // cos(candidate.angle()), host libm
-    thy += C.a(e[i].idx).sine * sc;
-    ssum += sc;
-    count++;
-  }
-  o.front_idx = (int32_t)e[0].idx;
-  o.count = count;
-  o.best_score = best;
-  o.thx = thx;
-  o.thy = thy;
-  o.ssum = ssum;
-  o.best_x = count > 1 ? ax / ssum : C.x(e[0].idx);
-  o.best_y = count > 1 ? ay / ssum : C.y(e[0].idx);
-  const double bound = std::min(best - 0.1, 0.5);
+  // FindBestCandidate (:670-710) over the sorted entries
+  struct Scores {
+    const Entry* e;
+    double operator[](int i) const { return e[i].score; }
+  };
+  struct Indices {
+    const Entry* e;
+    int64_t operator[](int i) const { return e[i].idx; }
+  };
+  const csm::CandGrid g = C.grid();
+  auto cos_sin = [&](int a) { return csm::CosSin{C.angles[a].cosine, C.angles[a].sine}; };  // host libm
+  double bx, by;
+  csm::find_best(Scores{e.data()}, Indices{e.data()}, (int)n, best, g, cos_sin, &o, &bx, &by);
+  const double bound = csm::cov_bound(best);
   // ComputePositionalCovariance's candidates (:915-928)
   o.n_pos = 0;
   for (size_t i = 0; i < e.size() && o.n_pos < csm::kCovPoints; ++i) {
@@ -55,7 +47,7 @@ void host_sort_finish(const double* scores, const Dims& D, const CandGeom& C, co
   for (size_t i = 0; i < e.size() && o.n_ang < csm::kCovPoints; ++i) {
     if (!(e[i].score >= bound)) break;  // sorted: nothing later qualifies
     const int64_t idx = e[i].idx;
-    if (double_equal(C.x(idx), o.best_x, lin_tol) && double_equal(C.y(idx), o.best_y, lin_tol)) {
+    if (csm::near_best(C.x(idx), C.y(idx), o.best_x, o.best_y, lin_tol)) {
       o.ang_idx[o.n_ang] = (int32_t)idx;
       o.ang_score[o.n_ang] = e[i].score;
       o.n_ang++;

@@ -20,9 +20,24 @@
 
 #include <hip/hip_runtime.h>
 
+#include "csm_finish_rules.hpp"
 #include "csm_internal.hpp"
 
 namespace csm {
+
+// The max of v over the wave, in every lane.
+__device__ __forceinline__ double wave_max(double v) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const double t = __shfl_xor(v, o, 64);
+    v = (t > v) ? t : v;
+  }
+  return v;
+}
+// Where this lane appends among the lanes a ballot selected: base + the
+// selected lanes below it.
+__device__ __forceinline__ int ballot_slot(int base, uint64_t mm, int lane) {
+  return base + __popcll(mm & ((1ull << lane) - 1));
+}
 
 constexpr int kSysWriteThrough = 17;  // buffer cache policy sc0 | sc1: system-coherent, written through L2
 
@@ -79,7 +94,6 @@ namespace tail {
 
 constexpr int kCap = 128;     // compacted candidates (the positional set, the near-best set); more: exact pass
 constexpr int kAngles = 32;   // angle rows staged in LDS for FindBest's sums (more: read from memory)
-constexpr int kLevels = 8;    // thresholds best - {0.01, 0.02, ..., 0.64}, then everything > bound
 // The finisher's LDS, two 16-byte aligned regions of the scoring kernel:
 // A: compacted keys (+4 padding) | their indices | ranked indices;
 // B: ranked keys | FinishOut | angle cos | angle sin.
@@ -97,14 +111,6 @@ __device__ __forceinline__ void store_score(const LevelWork& L, double* p, doubl
     __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   else
     *p = v;
-}
-
-__device__ __forceinline__ double wave_max(double v) {
-  for (int o = 32; o > 0; o >>= 1) {
-    const double t = __shfl_xor(v, o, 64);
-    v = (t > v) ? t : v;
-  }
-  return v;
 }
 
 // Append window w to the exact pass's list. Block 0 of the launch clears the
@@ -151,7 +157,7 @@ __device__ __forceinline__ void finish(const LevelWork& L, const ScanWork& S, co
   if (lane == 0) __hip_atomic_store(T.win_ctr + w, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
   const int n = (int)A.n_cand;
-  const int ns = A.n_space, nss = ns * ns;
+  const int ns = A.n_space;
   const double* sc = scores + S.out_off;
   double* ck = reinterpret_cast<double*>(ldsA);
   int* ci = reinterpret_cast<int*>(ldsA + (kCap + 4) * 8);
@@ -160,8 +166,8 @@ __device__ __forceinline__ void finish(const LevelWork& L, const ScanWork& S, co
   FinishOut* so = reinterpret_cast<FinishOut*>(ldsB + kCap * 8);
   double* acs = reinterpret_cast<double*>(ldsB + kCap * 8 + sizeof(FinishOut));
   double* asn = acs + kAngles;
-  const bool want_pos = !(A.skip_lists & 1), want_ang = !(A.skip_lists & 2);
-  const int lists = (want_pos ? 1 : 0) | (want_ang ? 2 : 0);
+  const WantLists want = want_lists(A.skip_lists);
+  const bool want_pos = want.pos, want_ang = want.ang;
 
   // 1. best = the front of the sorted candidates (:607): the angles' maxima
   double best = -INFINITY;
@@ -173,17 +179,7 @@ __device__ __forceinline__ void finish(const LevelWork& L, const ScanWork& S, co
   }
   best = wave_max(best);
   bool flag = __ballot(bad) != 0 || n <= 0;
-  const double lo = best - 0.1;
-  const double bound = (0.5 < lo) ? 0.5 : lo;  // std::min(best - 0.1, 0.5) (:912,:986)
-  // level k < 7: s > bound and s - best >= -0.01 * 2^k; level 7: s > bound
-  auto level_of = [&](double s) {
-    const double d = s - best;
-    double dl = 0.01;
-    int lv = 0;
-#pragma unroll
-    for (int k = 0; k < kLevels - 1; ++k, dl *= 2.0) lv += (d < -dl) ? 1 : 0;
-    return (s > bound) ? lv : kLevels;
-  };
+  const double bound = cov_bound(best);
   constexpr int U = 8;  // score loads in flight per lane
   // 2. one pass over the scores: level counts (16 bits a level per lane, two
   // 64-bit words) and, speculatively, the candidates of levels 0..kSpec
@@ -193,7 +189,7 @@ __device__ __forceinline__ void finish(const LevelWork& L, const ScanWork& S, co
   constexpr int kSpec = 3;
   int Lsel = 0, nC = 0, nS = 0;
   if (!flag) {
-    uint64_t c0 = 0, c1 = 0;
+    LevelCounts lc;
     for (int base = 0; base < n; base += 64 * U) {
       double v[U];
 #pragma unroll
@@ -204,14 +200,12 @@ __device__ __forceinline__ void finish(const LevelWork& L, const ScanWork& S, co
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int i = base + 64 * u + lane;
-        const int lv = level_of(v[u]);  // -INFINITY padding: no level
-        const uint64_t one = 1ull << (16 * (lv & 3));
-        c0 += lv < 4 ? one : 0ull;
-        c1 += (lv >= 4 && lv < kLevels) ? one : 0ull;
+        const int lv = level_of(v[u], best, bound);  // -INFINITY padding: no level
+        lc.add(lv);
         const bool in = lv <= kSpec;
         const uint64_t mm = __ballot(in);
         if (in) {
-          const int p = nS + __popcll(mm & ((1ull << lane) - 1));
+          const int p = ballot_slot(nS, mm, lane);
           if (p < kCap) {
             ck[p] = v[u];
             ci[p] = i;
@@ -222,22 +216,13 @@ __device__ __forceinline__ void finish(const LevelWork& L, const ScanWork& S, co
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
-      c0 += __shfl_xor(c0, o, 64);
-      c1 += __shfl_xor(c1, o, 64);
+      lc.c0 += __shfl_xor(lc.c0, o, 64);
+      lc.c1 += __shfl_xor(lc.c1, o, 64);
     }
-    int cnt[kLevels];
+    int cnt[kFinishLevels];
 #pragma unroll
-    for (int k = 0; k < kLevels; ++k) cnt[k] = (int)(((k < 4 ? c0 : c1) >> (16 * (k & 3))) & 0xFFFF);
-    Lsel = want_pos ? kLevels - 1 : 0;
-    int cum = 0;
-    for (int k = 0; want_pos && k < kLevels; ++k) {
-      cum += cnt[k];
-      if (cum >= kCovPoints) {
-        Lsel = k;
-        break;
-      }
-    }
-    for (int k = 0; k <= Lsel; ++k) nC += cnt[k];
+    for (int k = 0; k < kFinishLevels; ++k) cnt[k] = lc.level(k);
+    select_level(cnt, want_pos, &Lsel, &nC);
     flag = nC > kCap;
   }
   // 3. the set, compacted, ranked by value: rank = elements greater; an
@@ -250,11 +235,11 @@ __device__ __forceinline__ void finish(const LevelWork& L, const ScanWork& S, co
         const int t = t0 + lane;
         const double x = t < nS ? ck[t] : -INFINITY;
         const int ix = t < nS ? ci[t] : 0;
-        const bool in = t < nS && level_of(x) <= Lsel;
+        const bool in = t < nS && level_of(x, best, bound) <= Lsel;
         const uint64_t mm = __ballot(in);
         __syncthreads();  // every lane has read its entry before the list is rewritten
         if (in) {
-          const int p = at + __popcll(mm & ((1ull << lane) - 1));
+          const int p = ballot_slot(at, mm, lane);
           ck[p] = x;
           ci[p] = ix;
         }
@@ -273,10 +258,10 @@ __device__ __forceinline__ void finish(const LevelWork& L, const ScanWork& S, co
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int i = base + 64 * u + lane;
-          const bool in = level_of(v[u]) <= Lsel;  // padding never qualifies
+          const bool in = level_of(v[u], best, bound) <= Lsel;  // padding never qualifies
           const uint64_t mm = __ballot(in);
           if (in) {
-            const int p = at + __popcll(mm & ((1ull << lane) - 1));
+            const int p = ballot_slot(at, mm, lane);
             ck[p] = v[u];
             ci[p] = i;
           }
@@ -289,24 +274,16 @@ __device__ __forceinline__ void finish(const LevelWork& L, const ScanWork& S, co
     bool tie = false;
     for (int t = lane; t < nC; t += 64) {
       const double x = ck[t];
-      int r = 0, eq = 0;
-      for (int j = 0; j < nC; j += 4) {
-        const double2 u01 = *reinterpret_cast<const double2*>(&ck[j]);
-        const double2 u23 = *reinterpret_cast<const double2*>(&ck[j + 2]);
-        r += ((u01.x > x) ? 1 : 0) + ((u01.y > x) ? 1 : 0) + ((u23.x > x) ? 1 : 0) + ((u23.y > x) ? 1 : 0);
-        eq += ((u01.x == x) ? 1 : 0) + ((u01.y == x) ? 1 : 0) + ((u23.x == x) ? 1 : 0) + ((u23.y == x) ? 1 : 0);
-      }
-      const double d = x - best;
-      const bool inF = d < 0.0 ? d >= -1e-2 : d <= 1e-2;  // DoubleEqual(s, best, 1e-2)
-      tie |= eq > 1 && (inF || (want_pos && r <= kCovPoints));
+      int r, eq;
+      rank_among(ck, nC, x, &r, &eq);
+      tie |= tie_matters_positional(eq, r, in_response_band(x, best), want_pos);
       sk[r] = x;  // distinct ranks whenever nothing is flagged
       si[r] = ci[t];
     }
     flag = __ballot(tie) != 0;
   }
   const double f = A.step_cells;
-  auto cx = [&](int idx) { return S.x0 + ((idx / ns) % ns) * f; };
-  auto cy = [&](int idx) { return S.y0 + (idx % ns) * f; };
+  const CandGrid g{S.x0, S.y0, f, ns};
   if (!flag) {
     for (int t = lane; t < na && t < kAngles; t += 64) {
       const AngleEntry ae = angles[S.angle_off + t];
@@ -314,42 +291,13 @@ __device__ __forceinline__ void finish(const LevelWork& L, const ScanWork& S, co
       asn[t] = ae.sine;
     }
     __syncthreads();
-    // FindBestCandidate (:676-707), the same sequential sums as finish_kernel
     double bxl = 0.0, byl = 0.0;
     if (lane == 0) {
-      double ax = 0.0, ay = 0.0, thx = 0.0, thy = 0.0, ssum = 0.0;
-      int count = 0;
-      for (int r = 0; r < nC; ++r) {
-        const double s = sk[r];
-        const double d = s - best;
-        if (!(d < 0.0 ? d >= -1e-2 : d <= 1e-2)) break;
-        const int idx = si[r];
-        const int aa = idx / nss;
-        const double ca = aa < kAngles ? acs[aa] : angles[S.angle_off + aa].cosine;
-        const double sa = aa < kAngles ? asn[aa] : angles[S.angle_off + aa].sine;
-        ax += cx(idx) * s;
-        ay += cy(idx) * s;
-        thx += ca * s;
-        thy += sa * s;
-        ssum += s;
-        count++;
-      }
-      const int fi0 = si[0];
-      so->front_idx = fi0;
-      so->count = count;
-      so->best_score = best;
-      so->thx = thx;
-      so->thy = thy;
-      so->ssum = ssum;
-      if (count > 1) {
-        bxl = ax / ssum;
-        byl = ay / ssum;
-      } else {
-        bxl = cx(fi0);
-        byl = cy(fi0);
-      }
-      so->best_x = bxl;
-      so->best_y = byl;
+      auto cos_sin = [&](int aa) {  // the staged rows, memory past them
+        return CosSin{aa < kAngles ? acs[aa] : angles[S.angle_off + aa].cosine,
+                      aa < kAngles ? asn[aa] : angles[S.angle_off + aa].sine};
+      };
+      find_best(sk, si, nC, best, g, cos_sin, so, &bxl, &byl);
       so->n_pos = want_pos ? min(nC, kCovPoints) : 0;
     }
     const double bx = __shfl(bxl, 0, 64), by = __shfl(byl, 0, 64);
@@ -387,15 +335,10 @@ __device__ __forceinline__ void finish(const LevelWork& L, const ScanWork& S, co
           v = load_sc1(sc + i);
         }
         bool in = false;
-        if (v >= bound) {  // padding (-inf) never qualifies
-          const double dx = cx(i) - bx, dy = cy(i) - by;
-          const bool ex = dx < 0.0 ? dx >= -fabs(tol) : dx <= fabs(tol);
-          const bool ey = dy < 0.0 ? dy >= -fabs(tol) : dy <= fabs(tol);
-          in = ex && ey;
-        }
+        if (v >= bound) in = near_best(g.x(i), g.y(i), bx, by, tol);  // padding (-inf) never qualifies
         const uint64_t mm = __ballot(in);
         if (in) {
-          const int p = nN + __popcll(mm & ((1ull << lane) - 1));
+          const int p = ballot_slot(nN, mm, lane);
           if (p < kCap) {
             ck[p] = v;
             ci[p] = i;
@@ -411,14 +354,9 @@ __device__ __forceinline__ void finish(const LevelWork& L, const ScanWork& S, co
         bool tie = false;
         for (int t = lane; t < nN; t += 64) {
           const double x = ck[t];
-          int r = 0, eq = 0;
-          for (int j = 0; j < nN; j += 4) {
-            const double2 u01 = *reinterpret_cast<const double2*>(&ck[j]);
-            const double2 u23 = *reinterpret_cast<const double2*>(&ck[j + 2]);
-            r += ((u01.x > x) ? 1 : 0) + ((u01.y > x) ? 1 : 0) + ((u23.x > x) ? 1 : 0) + ((u23.y > x) ? 1 : 0);
-            eq += ((u01.x == x) ? 1 : 0) + ((u01.y == x) ? 1 : 0) + ((u23.x == x) ? 1 : 0) + ((u23.y == x) ? 1 : 0);
-          }
-          tie |= eq > 1 && r <= kCovPoints;
+          int r, eq;
+          rank_among(ck, nN, x, &r, &eq);
+          tie |= tie_matters_angular(eq, r);
           if (r < kCovPoints) {
             so->ang_idx[r] = ci[t];
             so->ang_score[r] = x;
@@ -431,7 +369,7 @@ __device__ __forceinline__ void finish(const LevelWork& L, const ScanWork& S, co
   }
   if (!flag) {
     __syncthreads();  // the LDS FinishOut is complete
-    emit_sealed(A, so, T.out + w, lists, kSealFast, lane);
+    emit_sealed(A, so, T.out + w, want.lists, kSealFast, lane);
     if (lane == 0) A.need_exact[w] = 0;
   } else if (lane == 0) {  // the exact pass takes this window
     A.need_exact[w] = 1;

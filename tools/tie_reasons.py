@@ -1,7 +1,9 @@
 """Why windows need the exact std::sort pass, on the
 CPU: the oracle's scores of every window of the 3-level match at the
-bench's configuration, classified with the fast finish's own decisions
-(csm_tail.hpp finish(), csm_finish.hip finish_fast_body): which lists each
+bench's configuration, classified with the fast finish's decisions. The rules
+live in csrc/csm_finish_rules.hpp (the finishes call them; tests/
+test_finish_rules.py pins them on the CPU); this is an independent statement
+of them in Python, used to pick test inputs: which lists each
 level keeps (live_lists + own_lists_skip), the FindBest band
 |s - best| <= 0.01, the positional set (the first 20 sorted candidates above
 min(best - 0.1, 0.5)), the angular set (candidates within the linear
