@@ -33,9 +33,8 @@
 #include <cstdint>
 #include <cstdlib>
 
-#include "csm_device.hpp"
-#include "csm_tail.hpp"
 #include "csm_internal.hpp"
+#include "csm_score_sink.hpp"
 
 namespace csm {
 namespace {
@@ -283,45 +282,18 @@ __device__ __forceinline__ void box_epilogue(const LevelWork& L, const ScanWork&
                                              BestPartial* __restrict__ partials, const AngleEntry* angles,
                                              char* ldsA, char* ldsB) {
   const double f = L.step_cells;
-  double bs = -1.0e300;
-  int64_t bf = INT64_MAX;
-  double lmax = -INFINITY;  // the fused finish (csm_tail.hpp): this lane's max, any NaN
-  bool lnan = false;
+  dev::ScoreSink<BEST> sink;
   const double yk = S.y0 + (oy + k) * f;  // :572
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
     const int j = 4 * q + t;
     if (act && j < NS) {
-      const double accd = (double)(acc[t] + (int64_t)S.n_used * L.outside_i) * L.int_scale;
+      const double accd = dev::fixed_point_acc(L, acc[t], S.n_used);
       const double xj = S.x0 + (ox + j) * f;  // :569
-      const double score = dev::penalized(L, S, accd, xj, yk, ae.angle);
-      const int64_t flat = ((int64_t)a * nsf + ox + j) * nsf + oy + k;
-      if (BEST) {
-        if (dev::better(score, flat, bs, bf)) {
-          bs = score;
-          bf = flat;
-        }
-      } else {
-        tail::store_score(L, out + S.out_off + flat, score);
-        lnan |= score != score;
-        lmax = (score > lmax) ? score : lmax;
-      }
+      sink.add(L, S, out, ((int64_t)a * nsf + ox + j) * nsf + oy + k, dev::penalized(L, S, accd, xj, yk, ae.angle));
     }
   }
-  if (BEST) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double os = __shfl_down(bs, o, 64);
-      const int64_t of = __shfl_down(bf, o, 64);
-      if (dev::better(os, of, bs, bf)) {
-        bs = os;
-        bf = of;
-      }
-    }
-    if (threadIdx.x == 0) partials[(int64_t)win * L.blocks_per_scan + a] = BestPartial{bs, bf};
-  } else if (L.tail.on) {
-    tail::finish(L, S, angles, out, a, lmax, lnan, ldsA, ldsB);
-  }
+  sink.done(L, S, angles, out, a, partials + (int64_t)win * L.blocks_per_scan + a, ldsA, ldsB);
 }
 
 template <int NS, int D, bool BEST>
@@ -361,10 +333,7 @@ __global__ __launch_bounds__(64) void score_box_kernel(LevelWork L, const ScanWo
   const int n_used = S.n_used;
   const int zero_off = B.zero_off;
   const int32_t* gi = L.gridi + (int64_t)S.grid_index * L.gridi_stride;
-  const uint32_t glo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)gi);
-  const uint32_t ghi = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)gi >> 32));
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(((uint64_t)ghi << 32) | glo), (short)0, (int)(L.gridi_stride * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = dev::uniform_rsrc(gi, (int)(L.gridi_stride * 4));
   const int voff = k * pitch4 + 16 * q;
 
   auto load = [&](int soff) { return __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0); };
@@ -543,10 +512,7 @@ __global__ CSM_PAIR_BOUNDS void score_box_pair_kernel(LevelWork L, const ScanWor
     tab[i] = (ia < L.pal_n && ib < L.pal_n) ? (double)L.pal_vals[ia] + (double)L.pal_vals[ib] : 0.0;
   }
   const uint8_t* pg = L.pal_strips + (int64_t)S.grid_index * L.strip_grid_bytes;
-  const uint32_t plo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)pg);
-  const uint32_t phi = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)pg >> 32));
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(((uint64_t)phi << 32) | plo), (short)0, (int)L.strip_grid_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = dev::uniform_rsrc(pg, (int)L.strip_grid_bytes);
   // rows past the box read the last row again (no new lines); their lanes'
   // sums are never read (the exchange below takes rows k < NS only)
   const int krow = min(k, NS - 1) * 16;

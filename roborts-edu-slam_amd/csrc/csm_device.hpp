@@ -8,19 +8,20 @@
 namespace csm {
 namespace dev {
 
+// The exact list's header {count, tag} (LevelWork::clear_word, SplitWork's):
+// block 0, thread 0 of a scoring kernel clears it to {0, tag}. An agent-scope
+// store: the fused finish's appends (csm_tail.hpp list_append) on other XCDs
+// wait for it and add to the same word inside this launch, so it must not sit
+// dirty in block 0's XCD L2 (a later write-back would also undo their adds).
+__device__ __forceinline__ void clear_word(int32_t* word, int32_t tag) {
+  if (word && blockIdx.x == 0 && threadIdx.x == 0)
+    __hip_atomic_store(reinterpret_cast<uint64_t*>(word), (uint64_t)(uint32_t)tag << 32, __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void clear_word(const LevelWork& L) { clear_word(L.clear_word, L.clear_tag); }
+
 // XCD-aware, bijective block remap (cdna_hip_programming.md T1): blocks that
 // share a logical neighbourhood (one window) land on one XCD's L2.
-// LevelWork::clear_word: block 0, lane 0 of a scoring kernel clears it. An
-// agent-scope store: the fused finish's appends (csm_tail.hpp list_append) on
-// other XCDs wait for it and add to the same word inside this launch, so it
-// must not sit dirty in block 0's XCD L2 (a later write-back would also undo
-// their adds).
-__device__ __forceinline__ void clear_word(const LevelWork& L) {
-  if (L.clear_word && blockIdx.x == 0 && threadIdx.x == 0)
-    __hip_atomic_store(reinterpret_cast<uint64_t*>(L.clear_word), (uint64_t)(uint32_t)L.clear_tag << 32,
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // {count 0, tag}
-}
-
 __device__ __forceinline__ int xcd_remap(int orig, int nwg) {
   const int xcd = orig & 7;
   const int q = nwg >> 3, r = nwg & 7;
@@ -53,6 +54,15 @@ __device__ __forceinline__ double penalized(const LevelWork& L, const ScanWork& 
 
 __device__ __forceinline__ bool better(double s, int64_t f, double bs, int64_t bf) {
   return (s > bs) || (s == bs && f < bf);
+}
+
+// A raw buffer descriptor over `bytes` bytes at p, which every lane of the wave
+// holds alike: readfirstlane keeps the base in scalar registers. Offsets
+// outside [0, bytes) fail the range check (loads read 0, stores are dropped).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t uniform_rsrc(const void* p, int bytes) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)p);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)p >> 32));
+  return __builtin_amdgcn_make_buffer_rsrc((void*)(((uint64_t)hi << 32) | lo), (short)0, bytes, 0x00020000);
 }
 
 // 16-byte buffer load written straight into LDS at lds + 16 * lane. The

@@ -72,7 +72,7 @@ __device__ __forceinline__ void raise_prob(float* prob, int64_t i, float p) {
   if (prob[i] < p) atomicMax(reinterpret_cast<unsigned int*>(prob + i), __float_as_uint(p));
 }
 // The fixed-point mirror (GmCells::fpm) of a cell: the fixed_point_kernel's
-// expression (csm_kernels.hip). The map is monotone in the value, so raising
+// expression (csm_gridprep.hip). The map is monotone in the value, so raising
 // the mirror to the max of the raises keeps it equal to the raised cell.
 __device__ __forceinline__ int32_t fixed_of(const GmCells& C, float p) {
   return (int32_t)(((double)p - (double)C.fpm_outside) * C.fpm_scale);

@@ -323,7 +323,7 @@ constexpr int kPalMaxSpace = 13;
 // into idx. scratch: pal_scratch_ints(n) ints.
 int64_t pal_scratch_ints(int64_t n);
 // max over n points (x, y) of |x| + |y| (NaN if any is NaN) as the bits of a
-// non-negative double, max-ed into *out (zeroed by the caller)
+// non-negative double, max-ed into *out (zeroed by the caller; csm_gridprep.hip)
 hipError_t launch_points_maxabs(const double* pts, int64_t n, unsigned long long* out, hipStream_t stream);
 // Raw laser ranges to endpoints (csm_ranges.hip): the kept beams (range_min <
 // r < threshold) of each of n_scans scans of n_beams ranges counted, the
@@ -455,7 +455,7 @@ hipError_t launch_angle_rows(const ScanWork* d_sw, int nw, int n_angles, double 
 constexpr int kGridiPadCols = 15;
 constexpr int kGridiPadRows = 16;
 constexpr int32_t gridi_pitch(int32_t sx) { return (sx + kGridiPadCols + 3) & ~3; }
-// Grid statistics for the exact integer path (csm_set_grid).
+// Grid statistics for the exact integer path (csm_set_grid; csm_gridprep.hip).
 struct GridStats {
   int32_t min_gexp;       // every nonzero |v| is a multiple of 2^min_gexp
   uint32_t max_abs_bits;  // bits of max |v| (positive floats order as integers)

@@ -4,9 +4,10 @@
 // MultiResolutionCorrelateScanMatcher::ScanMatch / GetResponse
 // (correlate_scan_matcher.h:552-584, 637-662) plus PenalizeResponse (:718-745).
 //
-// The general-purpose kernels, the fallbacks of the specialised families
-// (csm_box.hip one-cell steps, csm_phase.hip sub-cell steps, csm_tiny.hip
-// sub-cell spans, csm_split.hip few-window launches):
+// The general-purpose scoring kernels, the fallbacks of the specialised
+// families (csm_box.hip one-cell steps, csm_phase.hip sub-cell steps,
+// csm_tiny.hip sub-cell spans, csm_split.hip few-window launches), and nothing
+// else (grid and batch preparation: csm_gridprep.hip):
 //   v2 score_cols_kernel   any window and any grid: lane = (theta, x) column,
 //                          fp64 sums in the reference's beam order for any fp32
 //                          grid, or exact fixed-point sums (INT mode)
@@ -22,55 +23,13 @@
 #include <hip/hip_runtime.h>
 
 #include "csm_internal.hpp"
+#include "csm_score_sink.hpp"
 
 #pragma clang fp contract(off)
 
 namespace csm {
 
 namespace {
-
-// XCD-aware, bijective block remap (cdna_hip_programming.md T1): blocks that
-// share a logical neighbourhood (one window) land on one XCD's L2.
-// LevelWork::clear_word: block 0, lane 0 of a scoring kernel clears it.
-__device__ __forceinline__ void clear_word(const LevelWork& L) {
-  if (L.clear_word && blockIdx.x == 0 && threadIdx.x == 0)
-    __hip_atomic_store(reinterpret_cast<uint64_t*>(L.clear_word), (uint64_t)(uint32_t)L.clear_tag << 32,
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // {count 0, tag} (dev::clear_word)
-}
-
-__device__ __forceinline__ int xcd_remap(int orig, int nwg) {
-  const int xcd = orig & 7;
-  const int q = nwg >> 3, r = nwg & 7;
-  const int base = (xcd < r) ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
-  return base + (orig >> 3);
-}
-
-// Divisor (:659) and centre penalty (:718-745) of one candidate.
-__device__ __forceinline__ double penalized(const LevelWork& L, const ScanWork& S, double acc,
-                                           double x, double y, double angle) {
-  double score = acc / S.divisor;
-  if (L.use_penalty) {
-    // util::DoubleEqual(score, 0.0) with kDoubleTolerance = 1e-6.
-    const bool is_zero = (score < 0.0) ? (score >= -1e-06) : (score <= 1e-06);
-    if (!is_zero) {
-      const double dx = x - S.cx, dy = y - S.cy;
-      double d2 = dx * dx + dy * dy;
-      d2 *= (L.mres * L.mres);
-      double dp = 1.0 - (L.dist_gain * d2 / (L.size / 2));
-      dp = dp < 0.5 ? 0.5 : dp;  // std::max(dp, 0.5)
-      double da = angle - S.ct;
-      da = da * da;
-      double ap = 1.0 - (0.25 * da / 0.349);
-      ap = ap < 0.9 ? 0.9 : ap;
-      score = score * (dp * ap);
-    }
-  }
-  return score;
-}
-
-__device__ __forceinline__ bool better(double s, int64_t f, double bs, int64_t bf) {
-  return (s > bs) || (s == bs && f < bf);
-}
 
 // ---- v2: column kernel ------------------------------------------------------
 // One wave per block; lane = one (theta, x) column of the window, KT rows of
@@ -91,8 +50,8 @@ __global__ __launch_bounds__(64) void score_cols_kernel(
     LevelWork L, const ScanWork* __restrict__ scans, const double2* __restrict__ pts,
     const AngleEntry* __restrict__ angles, double* __restrict__ out,
     BestPartial* __restrict__ partials) {
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  clear_word(L);
+  const int bid = dev::xcd_remap(blockIdx.x, gridDim.x);
+  dev::clear_word(L);
   const int win = bid / L.blocks_per_scan;
   const int r = bid - win * L.blocks_per_scan;
   const int cb = r / L.ktiles;
@@ -124,11 +83,7 @@ __global__ __launch_bounds__(64) void score_cols_kernel(
   }
   if (INT) {
     const int32_t* gi = L.gridi + (int64_t)S.grid_index * L.gridi_stride;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)gi);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)gi >> 32));
-    const int32_t* gbase = (const int32_t*)(((uint64_t)hi << 32) | lo);
-    const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void*)gbase, (short)0, (int)(L.gridi_stride * 4), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc = dev::uniform_rsrc(gi, (int)(L.gridi_stride * 4));
     const int sx4 = L.pitch * 4;  // row stride of gridi (bytes)
     // Cells of beam b for every row of this lane (KT buffer loads in flight).
     // The host guarantees |gy| * 4 * pitch < 2^30 for every candidate of the
@@ -206,48 +161,18 @@ __global__ __launch_bounds__(64) void score_cols_kernel(
     }
   }
   const int krem = min(KT, L.n_space - k0);
-  double bs = -1.0e300;
-  int64_t bf = INT64_MAX;
+  dev::ScoreSink<BEST> sink;
 #pragma unroll
   for (int kk = 0; kk < KT; ++kk) {
     if (kk < krem && valid) {
-      const double acc =
-          INT ? (double)(acci[kk] + (int64_t)n_used * L.outside_i) * L.int_scale : accd[kk];
-      const double score = penalized(L, S, acc, x, y[kk], ae.angle);
-      const int64_t flat = ((int64_t)a * L.n_space + j) * L.n_space + (k0 + kk);
-      if (BEST) {
-        if (better(score, flat, bs, bf)) {
-          bs = score;
-          bf = flat;
-        }
-      } else {
-        out[S.out_off + flat] = score;
-      }
+      const double acc = INT ? dev::fixed_point_acc(L, acci[kk], n_used) : accd[kk];
+      sink.add(L, S, out, ((int64_t)a * L.n_space + j) * L.n_space + (k0 + kk),
+               dev::penalized(L, S, acc, x, y[kk], ae.angle));
     }
   }
-  if (BEST) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const double os = __shfl_down(bs, off, 64);
-      const int64_t of = __shfl_down(bf, off, 64);
-      if (better(os, of, bs, bf)) {
-        bs = os;
-        bf = of;
-      }
-    }
-    if (lane == 0) partials[(int64_t)win * L.blocks_per_scan + r] = BestPartial{bs, bf};
-  }
-}
-
-// 16-byte buffer load written straight into LDS at lds + 16 * lane. The
-// builtin has no host-side form; the guard only keeps hipcc's host pass (which
-// must still emit the kernel's launch stub) from seeing it.
-__device__ __forceinline__ void buffer_load_lds16(__amdgpu_buffer_rsrc_t rsrc,
-                                                  __attribute__((address_space(3))) int32_t* lds,
-                                                  int voffset) {
-#if defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, lds, 16, voffset, 0, 0, 0);
-#endif
+  // all mode ends with the stores: a block's lanes span angles, so there is no
+  // fused finish here (level_decide never sets tail.on for this kernel)
+  if constexpr (BEST) sink.done(L, S, angles, out, a, partials + (int64_t)win * L.blocks_per_scan + r, nullptr, nullptr);
 }
 
 // ---- v4: row-segment kernel, LDS-DMA staging (INT mode) --------------------
@@ -302,8 +227,8 @@ __global__ __launch_bounds__(64 * BS) void score_rowsd_kernel(
   __shared__ __attribute__((aligned(16))) int32_t img2_s[BS * IMG];
   __shared__ __attribute__((aligned(16))) int32_t zblk[NS * SEG];
   __shared__ int64_t xsum[(BS - 1) * 64 * NS + 1];  // waves 1.. -> wave 0
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  clear_word(L);
+  const int bid = dev::xcd_remap(blockIdx.x, gridDim.x);
+  dev::clear_word(L);
   const int win = bid / L.blocks_per_scan;
   const int blk = bid - win * L.blocks_per_scan;
   const ScanWork S = scans[win];
@@ -334,10 +259,7 @@ __global__ __launch_bounds__(64 * BS) void score_rowsd_kernel(
   const int b_lo = (int)((int64_t)n_used * wv / BS);  // this wave's beams
   const int b_hi = (int)((int64_t)n_used * (wv + 1) / BS);
   const int32_t* gi = L.gridi + (int64_t)S.grid_index * L.gridi_stride;
-  const uint32_t glo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)gi);
-  const uint32_t ghi = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)gi >> 32));
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(((uint64_t)ghi << 32) | glo), (short)0, (int)(L.gridi_stride * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = dev::uniform_rsrc(gi, (int)(L.gridi_stride * 4));
   const int pitch4 = pitch * 4;
   const int zero_off = sy * pitch4;  // byte offset of the appended zero row
 
@@ -358,17 +280,11 @@ __global__ __launch_bounds__(64 * BS) void score_rowsd_kernel(
   // LDS queue) per beam.
   double2 pw = P[(int64_t)max(0, min(b_lo + lane, b_hi - 1)) * step];
   int pbase = b_lo;
-  auto bcast = [](double v, int l) {
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)u, l);
-    const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(u >> 32), l);
-    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-  };
   auto point = [&](int b) {
     const int l = b - pbase;
     double2 p;
-    p.x = bcast(pw.x, l);
-    p.y = bcast(pw.y, l);
+    p.x = dev::bcast_lane(pw.x, l);
+    p.y = dev::bcast_lane(pw.y, l);
     return p;
   };
 
@@ -387,7 +303,7 @@ __global__ __launch_bounds__(64 * BS) void score_rowsd_kernel(
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
       const int o = __builtin_amdgcn_ds_bpermute(src4[i], rowoff);
-      buffer_load_lds16(rsrc, (lds_i32*)(image(buf) + i * 256), qofs[i] < 0 ? zero_off : o + qofs[i]);
+      dev::buffer_load_lds16(rsrc, (lds_i32*)(image(buf) + i * 256), qofs[i] < 0 ? zero_off : o + qofs[i]);
     }
     const int pos = ixr - xs;
     const bool inx = (unsigned)ixr < (unsigned)sx;
@@ -501,37 +417,19 @@ __global__ __launch_bounds__(64 * BS) void score_rowsd_kernel(
 #pragma unroll
       for (int k = 0; k < NS; ++k) acci[k] += xsum[((w2 - 1) * NS + k) * 64 + lane];
   }
-  double bs = -1.0e300;
-  int64_t bf = INT64_MAX;
+  dev::ScoreSink<BEST> sink;  // wave 0 alone from here on
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
     if (valid) {
-      const double acc = (double)(acci[k] + (int64_t)n_used * L.outside_i) * L.int_scale;
+      const double acc = dev::fixed_point_acc(L, acci[k], n_used);
       const double yk = S.y0 + k * f;  // :572
-      const double score = penalized(L, S, acc, x_r, yk, ae.angle);
-      const int64_t flat = ((int64_t)a * NS + r) * NS + k;
-      if (BEST) {
-        if (better(score, flat, bs, bf)) {
-          bs = score;
-          bf = flat;
-        }
-      } else {
-        out[S.out_off + flat] = score;
-      }
+      sink.add(L, S, out, ((int64_t)a * NS + r) * NS + k, dev::penalized(L, S, acc, x_r, yk, ae.angle));
     }
   }
-  if (BEST) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double os = __shfl_down(bs, o, 64);
-      const int64_t of = __shfl_down(bf, o, 64);
-      if (better(os, of, bs, bf)) {
-        bs = os;
-        bf = of;
-      }
-    }
-    if (lane == 0) partials[(int64_t)win * L.blocks_per_scan + blk] = BestPartial{bs, bf};
-  }
+  // all mode ends with the stores: a wave holds several angles, so there is no
+  // fused finish here (level_decide never sets tail.on for this kernel)
+  if constexpr (BEST)
+    sink.done(L, S, angles, out, a, partials + (int64_t)win * L.blocks_per_scan + blk, nullptr, nullptr);
 }
 
 __global__ __launch_bounds__(kBlock) void reduce_best_kernel(const BestPartial* __restrict__ in,
@@ -543,20 +441,12 @@ __global__ __launch_bounds__(kBlock) void reduce_best_kernel(const BestPartial* 
   int64_t bf = INT64_MAX;
   for (int i = threadIdx.x; i < per; i += kBlock) {
     const BestPartial p = in[w * per + i];
-    if (better(p.score, p.flat, bs, bf)) {
+    if (dev::better(p.score, p.flat, bs, bf)) {
       bs = p.score;
       bf = p.flat;
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const double os = __shfl_down(bs, off, 64);
-    const int64_t of = __shfl_down(bf, off, 64);
-    if (better(os, of, bs, bf)) {
-      bs = os;
-      bf = of;
-    }
-  }
+  dev::wave_best(bs, bf);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (lane == 0) {
     red_s[wave] = bs;
@@ -565,7 +455,7 @@ __global__ __launch_bounds__(kBlock) void reduce_best_kernel(const BestPartial* 
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int k = 1; k < kBlock / 64; ++k)
-      if (better(red_s[k], red_f[k], bs, bf)) {
+      if (dev::better(red_s[k], red_f[k], bs, bf)) {
         bs = red_s[k];
         bf = red_f[k];
       }
@@ -683,184 +573,11 @@ hipError_t launch_score_rows(const LevelWork& L, const ScanWork* d_scans, const 
   return hipErrorInvalidValue;
 }
 
-// max |x| + |y| over a batch's points (csm_load_scans_async): the bound
-// int_mode_ok needs, found on the device while the batch uploads instead of
-// by the host reading every point. Non-negative doubles order like their
-// bits, and a NaN's bits exceed +inf's, so an integer max keeps NaN.
-__global__ __launch_bounds__(256) void points_maxabs_kernel(const double2* __restrict__ p, int64_t n,
-                                                            unsigned long long* __restrict__ out) {
-  unsigned long long m = 0;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const double2 q = p[i];
-    const double a = fabs(q.x) + fabs(q.y);
-    const unsigned long long b = __builtin_bit_cast(unsigned long long, a);
-    m = b > m ? b : m;
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long t = __shfl_xor(m, o, 64);
-    m = t > m ? t : m;
-  }
-  if ((threadIdx.x & 63) == 0) atomicMax(out, m);
-}
-
-hipError_t launch_points_maxabs(const double* pts, int64_t n, unsigned long long* out, hipStream_t stream) {
-  if (n <= 0) return hipSuccess;
-  const int64_t blocks = (n + 255) / 256 < 1024 ? (n + 255) / 256 : 1024;
-  hipLaunchKernelGGL(points_maxabs_kernel, dim3((unsigned)blocks), dim3(256), 0, stream,
-                     reinterpret_cast<const double2*>(pts), n, out);
-  return hipGetLastError();
-}
-
 hipError_t launch_reduce_best(const BestPartial* d_partials, int32_t blocks_per_scan,
                               int32_t n_windows, BestPartial* d_out, hipStream_t stream) {
   if (n_windows <= 0) return hipErrorInvalidValue;
   hipLaunchKernelGGL(reduce_best_kernel, dim3(n_windows), dim3(kBlock), 0, stream, d_partials,
                      blocks_per_scan, d_out);
-  return hipGetLastError();
-}
-
-}  // namespace csm
-
-// ---- grid analysis / fixed-point copy (csm_set_grid) -----------------------
-namespace csm {
-namespace {
-
-// Per cell: finite? smallest power of two the value is a multiple of, and |v|.
-// Pass 1: each block reduces its cells in registers, then across its waves in
-// LDS, and writes one partial (no atomics: thousands of same-address atomics
-// serialised the old version at ~0.3 ms for a 3000 x 3000 map).
-__global__ __launch_bounds__(256) void analyze_grid_kernel(const float* __restrict__ g, int64_t n,
-                                                           GridStats* __restrict__ partials) {
-  int min_g = INT32_MAX;
-  uint32_t max_bits = 0;
-  int bad = 0;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const uint32_t u = __float_as_uint(g[i]) & 0x7FFFFFFFu;
-    const uint32_t e = u >> 23, m = u & 0x7FFFFFu;
-    if (e == 0xFF) {
-      bad = 1;
-      continue;
-    }
-    if (u == 0) continue;
-    const uint32_t mm = (e == 0) ? m : (m | 0x800000u);
-    const int gexp = ((e == 0) ? -149 : (int)e - 150) + __builtin_ctz(mm);
-    min_g = min(min_g, gexp);
-    max_bits = max(max_bits, u);
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    min_g = min(min_g, __shfl_down(min_g, off, 64));
-    max_bits = max(max_bits, (uint32_t)__shfl_down((int)max_bits, off, 64));
-    bad |= __shfl_down(bad, off, 64);
-  }
-  __shared__ GridStats w[4];
-  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = GridStats{min_g, max_bits, bad, 0};
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    GridStats r = w[0];
-    for (int k = 1; k < 4; ++k) {
-      r.min_gexp = min(r.min_gexp, w[k].min_gexp);
-      r.max_abs_bits = max(r.max_abs_bits, w[k].max_abs_bits);
-      r.nonfinite |= w[k].nonfinite;
-    }
-    partials[blockIdx.x] = r;
-  }
-}
-
-// Pass 2: one block folds the partials into st[0].
-__global__ __launch_bounds__(256) void analyze_reduce_kernel(const GridStats* __restrict__ partials, int np,
-                                                             GridStats* __restrict__ st) {
-  int min_g = INT32_MAX;
-  uint32_t max_bits = 0;
-  int bad = 0;
-  for (int i = threadIdx.x; i < np; i += blockDim.x) {
-    const GridStats p = partials[i];
-    min_g = min(min_g, p.min_gexp);
-    max_bits = max(max_bits, p.max_abs_bits);
-    bad |= p.nonfinite;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    min_g = min(min_g, __shfl_down(min_g, off, 64));
-    max_bits = max(max_bits, (uint32_t)__shfl_down((int)max_bits, off, 64));
-    bad |= __shfl_down(bad, off, 64);
-  }
-  __shared__ GridStats w[4];
-  if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = GridStats{min_g, max_bits, bad, 0};
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    GridStats r = w[0];
-    for (int k = 1; k < 4; ++k) {
-      r.min_gexp = min(r.min_gexp, w[k].min_gexp);
-      r.max_abs_bits = max(r.max_abs_bits, w[k].max_abs_bits);
-      r.nonfinite |= w[k].nonfinite;
-    }
-    st[0] = r;
-  }
-}
-
-// gi = (g - outside) * 2^E, exact when the host accepted E.
-// gi[y * pitch + x] = (g[y * sx + x] - outside) * 2^E; pad cells (x >= sx)
-// and the appended zero row y = sy (what DMA reads for rows off the grid) = 0.
-__global__ __launch_bounds__(256) void fixed_point_kernel(const float* __restrict__ g, int32_t sx,
-                                                          int32_t sy, int32_t pitch, float outside,
-                                                          double scale, int32_t* __restrict__ gi,
-                                                          int32_t pad_rows) {
-  const int64_t n = (int64_t)pitch * (sy + pad_rows);
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t y = i / pitch;
-    const int x = (int)(i - y * pitch);
-    gi[i] = (x < sx && y < sy) ? (int32_t)(((double)g[y * sx + x] - (double)outside) * scale) : 0;
-  }
-}
-
-}  // namespace
-
-hipError_t launch_analyze_grid(const float* g, int64_t n, GridStats* d_stats, hipStream_t stream) {
-  // d_stats holds 1 + kAnalyzeBlocks entries: the result, then the partials
-  const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, kAnalyzeBlocks));
-  hipLaunchKernelGGL(analyze_grid_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, g, n, d_stats + 1);
-  hipLaunchKernelGGL(analyze_reduce_kernel, dim3(1), dim3(256), 0, stream, d_stats + 1, (int)blocks, d_stats);
-  return hipGetLastError();
-}
-
-hipError_t launch_fixed_point(const float* g, int32_t sx, int32_t sy, int32_t pitch, float outside,
-                              int int_exp, int32_t* gi, hipStream_t stream, bool pad) {
-  const int32_t pad_rows = pad ? kGridiPadRows : 0;
-  const int64_t n = (int64_t)pitch * (sy + pad_rows);
-  const int64_t blocks = std::min<int64_t>((n + 255) / 256, 4096);
-  hipLaunchKernelGGL(fixed_point_kernel, dim3((unsigned)std::max<int64_t>(blocks, 1)), dim3(256), 0,
-                     stream, g, sx, sy, pitch, outside, ldexp(1.0, int_exp), gi, pad_rows);
-  return hipGetLastError();
-}
-
-namespace {
-// Incremental refresh of a resident grid (csm_update_grid_cells): each entry
-// rewrites one fp32 cell and, when the exact fixed-point copy exists, its
-// int32 image with the fixed_point_kernel's expression. Duplicate indices
-// carry the same value, so their order does not matter.
-__global__ __launch_bounds__(256) void update_cells_kernel(const CellUpdate* __restrict__ u, int64_t n,
-                                                           float* __restrict__ g, int32_t sx,
-                                                           int32_t* __restrict__ gi, int32_t pitch,
-                                                           float outside, double scale) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const CellUpdate c = u[i];
-    g[c.index] = c.value;
-    if (gi) {
-      const int32_t y = c.index / sx;
-      const int32_t x = c.index - y * sx;
-      gi[(int64_t)y * pitch + x] = (int32_t)(((double)c.value - (double)outside) * scale);
-    }
-  }
-}
-}  // namespace
-
-hipError_t launch_update_cells(const CellUpdate* d_updates, int64_t n, float* g, int32_t sx, int32_t* gi,
-                               int32_t pitch, float outside, int int_exp, hipStream_t stream) {
-  if (n <= 0) return hipSuccess;
-  const int64_t blocks = std::min<int64_t>((n + 255) / 256, 2048);
-  hipLaunchKernelGGL(update_cells_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, d_updates, n, g, sx, gi,
-                     pitch, outside, ldexp(1.0, int_exp));
   return hipGetLastError();
 }
 

@@ -35,9 +35,8 @@
 
 #include <cstdint>
 
-#include "csm_device.hpp"
-#include "csm_tail.hpp"
 #include "csm_internal.hpp"
+#include "csm_score_sink.hpp"
 
 namespace csm {
 namespace {
@@ -139,11 +138,8 @@ __global__ __launch_bounds__(64, CSM_PHASE_WAVES) void score_phase_kernel(LevelW
   const int n_used = S.n_used;
   const int32_t* gi = L.gridi + (int64_t)S.grid_index * L.gridi_stride;
   const int32_t* gsrc = ST ? L.istrips + (int64_t)S.grid_index * (L.istrip_grid_bytes / 4) : gi;
-  const uint32_t glo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)gsrc);
-  const uint32_t ghi = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)gsrc >> 32));
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(((uint64_t)ghi << 32) | glo), (short)0, ST ? (int)L.istrip_grid_bytes : (int)(L.gridi_stride * 4),
-      0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc =
+      dev::uniform_rsrc(gsrc, ST ? (int)L.istrip_grid_bytes : (int)(L.gridi_stride * 4));
   const int voff = ST ? cv * kRowB + ch * 16 : cv * pitch4 + ch * 16;
 
   for (int i = lane; i < NQ * kPhaseMaxSpace; i += 64) oxs[i / kPhaseMaxSpace][i % kPhaseMaxSpace] =
@@ -398,49 +394,21 @@ __global__ __launch_bounds__(64, CSM_PHASE_WAVES) void score_phase_kernel(LevelW
     }
   }
 
-  double bs = -1.0e300;
-  int64_t bf = INT64_MAX;
-  double lmax = -INFINITY;  // the fused finish (csm_tail.hpp): this lane's max, any NaN
-  bool lnan = false;
+  dev::ScoreSink<BEST> sink;
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const int t = lane + 64 * r;
     if (t < NC) {
       const int j = t / NS, k = t - (t / NS) * NS;
-      const double accd = (double)(sum[r] + (int64_t)n_used * L.outside_i) * L.int_scale;
+      const double accd = dev::fixed_point_acc(L, sum[r], n_used);
       const double xj = S.x0 + j * f;  // :569
       const double yk = S.y0 + k * f;  // :572
-      const double score = dev::penalized(L, S, accd, xj, yk, ae.angle);
-      const int64_t flat = ((int64_t)a * NS + j) * NS + k;
-      if (BEST) {
-        if (dev::better(score, flat, bs, bf)) {
-          bs = score;
-          bf = flat;
-        }
-      } else {
-        tail::store_score(L, out + S.out_off + flat, score);
-        lnan |= score != score;
-        lmax = (score > lmax) ? score : lmax;
-      }
+      sink.add(L, S, out, ((int64_t)a * NS + j) * NS + k, dev::penalized(L, S, accd, xj, yk, ae.angle));
     }
   }
-  if (!BEST && L.tail.on) {
-    __syncthreads();  // psum's last reads are done: the finisher's LDS
-    tail::finish(L, S, angles, out, a, lmax, lnan, reinterpret_cast<char*>(psum),
-                 reinterpret_cast<char*>(psum) + tail::kBytesA);
-  }
-  if (BEST) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double os = __shfl_down(bs, o, 64);
-      const int64_t of = __shfl_down(bf, o, 64);
-      if (dev::better(os, of, bs, bf)) {
-        bs = os;
-        bf = of;
-      }
-    }
-    if (lane == 0) partials[(int64_t)win * L.blocks_per_scan + a] = BestPartial{bs, bf};
-  }
+  if (!BEST && L.tail.on) __syncthreads();  // psum's last reads are done: the finisher's LDS
+  sink.done(L, S, angles, out, a, partials + (int64_t)win * L.blocks_per_scan + a, reinterpret_cast<char*>(psum),
+            reinterpret_cast<char*>(psum) + tail::kBytesA);
 }
 
 template <int NS, int C, int NQ, bool ST, int KCH>

@@ -20,7 +20,7 @@
 
 #include <cstdlib>
 
-#include "csm_device.hpp"
+#include "csm_score_sink.hpp"
 #include "csm_pyramid.hpp"
 
 #pragma clang fp contract(off)
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(256) void pyr_top_kernel(LevelWork L, int32_t nj, i
 // centre penalty's floor).
 __device__ __forceinline__ double level_bound(const LevelWork& L, const ScanWork& S, int64_t sum, int qs,
                                               int32_t n_used) {
-  const double acc = (double)((sum << qs) + (int64_t)n_used * L.outside_i) * L.int_scale;
+  const double acc = dev::fixed_point_acc(L, sum << qs, n_used);
   const double raw = acc / S.divisor;
   return (L.use_penalty && raw < 0.0) ? raw * 0.45 : raw;
 }
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(kPB) void pyr_bound_kernel(LevelWork L, PyrGrid lev
       const double x = S.x0 + j0 * L.step_cells;  // :569
       const double y = S.y0 + k0 * L.step_cells;  // :572
       sum <<= lev.qs;  // the quantised levels' unit
-      const double acc = (double)(sum + (int64_t)n_used * L.outside_i) * L.int_scale;
+      const double acc = dev::fixed_point_acc(L, sum, n_used);
       if (d == 0) {
         v = penalized(L, S, acc, x, y, ae.angle);
       } else {
@@ -313,7 +313,7 @@ __global__ __launch_bounds__(kTB) void pyr_top_bound_kernel(LevelWork L, PyrGrid
   for (int kk = 0; kk < kTopKT; ++kk) {
     if (valid && kk < krem) {
       const int K = K0 + kk;
-      const double acc = (double)((sum[kk] << lev.qs) + (int64_t)n_used * L.outside_i) * L.int_scale;
+      const double acc = dev::fixed_point_acc(L, sum[kk] << lev.qs, n_used);
       const double raw = acc / S.divisor;
       const double v = (L.use_penalty && raw < 0.0) ? raw * 0.45 : raw;
       const int64_t idx = (wbase + K) * nj + J;
@@ -395,10 +395,7 @@ __global__ __launch_bounds__(64) void pyr_topbox_kernel(LevelWork L, PyrGrid tb,
     voff[s] = ((Ks[s] << d) * pitch2) + 16 * cs[s];
   }
   const int16_t* g = (const int16_t*)tb.g + (int64_t)S.grid_index * tb.stride;
-  const uint32_t glo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)g);
-  const uint32_t ghi = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)g >> 32));
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(((uint64_t)ghi << 32) | glo), (short)0, (int)(tb.stride * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = dev::uniform_rsrc(g, (int)(tb.stride * 2));
   const double x_0 = S.x0 + 0 * L.step_cells;  // :569, J = 0
   const double y_0 = S.y0 + 0 * L.step_cells;  // :572, K = 0
   // element offset of the beam's node (0, 0) (zero_el: reads zeros)

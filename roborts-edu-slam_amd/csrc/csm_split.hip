@@ -28,8 +28,8 @@
 
 #include <cstdint>
 
-#include "csm_device.hpp"
 #include "csm_internal.hpp"
+#include "csm_score_sink.hpp"
 
 #pragma clang fp contract(off)
 
@@ -47,9 +47,7 @@ __global__ __launch_bounds__(kT) void score_split_kernel(LevelWork L, SplitWork 
   const int tid = threadIdx.x;
   CSM_TS_MIN(0);
   if (blockIdx.x == 0) {
-    if (W.clear_word && tid == 0)
-      __hip_atomic_store(reinterpret_cast<uint64_t*>(W.clear_word), (uint64_t)(uint32_t)W.clear_tag << 32,
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // {count 0, tag} (dev::clear_word)
+    dev::clear_word(W.clear_word, W.clear_tag);
     if (W.inline_window) {
       if (tid == 0) *W.scans_out = W.sw;
       for (int t = tid; t < L.n_angles; t += kT) W.angles_out[t] = W.ang[t];
@@ -88,10 +86,7 @@ __global__ __launch_bounds__(kT) void score_split_kernel(LevelWork L, SplitWork 
   const double y = S.y0 + k * f;  // :572
 
   const int32_t* gi = L.gridi + (int64_t)S.grid_index * L.gridi_stride;
-  const uint32_t glo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)gi);
-  const uint32_t ghi = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)gi >> 32));
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(((uint64_t)ghi << 32) | glo), (short)0, (int)(L.gridi_stride * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = dev::uniform_rsrc(gi, (int)(L.gridi_stride * 4));
   const int sx = L.size_x, sy = L.size_y;
   const int sx4 = L.pitch * 4;
   const double2* __restrict__ P = pts + S.pts_off;
@@ -130,10 +125,7 @@ __global__ __launch_bounds__(kT) void score_split_kernel(LevelWork L, SplitWork 
   // acquire fence pair here cost ~3.4 us on the level's critical path.
   const int64_t cidx = (int64_t)win * W.chunks + chunk;
   int32_t* slab = W.slab + cidx * W.splits * kT;
-  const uint32_t slo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)slab);
-  const uint32_t shi = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)slab >> 32));
-  const __amdgpu_buffer_rsrc_t srsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(((uint64_t)shi << 32) | slo), (short)0, W.splits * kT * 4, 0x00020000);
+  const __amdgpu_buffer_rsrc_t srsrc = dev::uniform_rsrc(slab, W.splits * kT * 4);
   constexpr int kSc1 = 16;  // cache policy sc1: write-through stores, L1-bypassing loads
   __builtin_amdgcn_raw_buffer_store_b32(acc, srsrc, (split * kT + tid) * 4, 0, kSc1);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -159,7 +151,7 @@ __global__ __launch_bounds__(kT) void score_split_kernel(LevelWork L, SplitWork 
     for (int u = 0; u < kUnroll; ++u) sum += v[u];
   }
   if (valid) {
-    const double accd = (double)(sum + (int64_t)S.n_used * L.outside_i) * L.int_scale;
+    const double accd = dev::fixed_point_acc(L, sum, S.n_used);
     out[S.out_off + q] = dev::penalized(L, S, accd, x, y, ae.angle);
   }
   CSM_TS_MAX(3);  // chunk reduced, scores written

@@ -23,9 +23,8 @@
 
 #include <cstdint>
 
-#include "csm_device.hpp"
-#include "csm_tail.hpp"
 #include "csm_internal.hpp"
+#include "csm_score_sink.hpp"
 
 namespace csm {
 namespace {
@@ -58,10 +57,7 @@ __global__ __launch_bounds__(64) void score_tiny_kernel(LevelWork L, const ScanW
   // the fast path's 2 x 2 block stays inside the zero padding
   const int gx_hi = pitch - 2, gy_hi = sy + kGridiPadRows - 2;
   const int32_t* gi = L.gridi + (int64_t)S.grid_index * L.gridi_stride;
-  const uint32_t glo = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)gi);
-  const uint32_t ghi = __builtin_amdgcn_readfirstlane((uint32_t)((uintptr_t)gi >> 32));
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(((uint64_t)ghi << 32) | glo), (short)0, (int)(L.gridi_stride * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = dev::uniform_rsrc(gi, (int)(L.gridi_stride * 4));
   const double2* __restrict__ P = pts + S.pts_off;
   const int n_used = S.n_used, step = S.step;
 
@@ -125,41 +121,18 @@ __global__ __launch_bounds__(64) void score_tiny_kernel(LevelWork L, const ScanW
       const int64_t v = dev::wave_sum_i64(acc[j][k] + part[j][k]);
       if (lane == j * NS + k) mine = v;
     }
-  double bs = -1.0e300;
-  int64_t bf = INT64_MAX;
-  double lmax = -INFINITY;  // the fused finish (csm_tail.hpp): this lane's max, any NaN
-  bool lnan = false;
+  dev::ScoreSink<BEST> sink;
   if (lane < NC) {
     const int j = lane / NS, k = lane - (lane / NS) * NS;
-    const double accd = (double)(mine + (int64_t)n_used * L.outside_i) * L.int_scale;
+    const double accd = dev::fixed_point_acc(L, mine, n_used);
     const double score = dev::penalized(L, S, accd, S.x0 + j * f /* :569 */, S.y0 + k * f /* :572 */, ae.angle);
-    const int64_t flat = ((int64_t)a * NS + j) * NS + k;
-    if (BEST) {
-      bs = score;
-      bf = flat;
-    } else {
-      tail::store_score(L, out + S.out_off + flat, score);
-      lnan = score != score;
-      lmax = score;
-    }
+    sink.add(L, S, out, ((int64_t)a * NS + j) * NS + k, score);
   }
-  if (!BEST && L.tail.on) {
-    __shared__ __attribute__((aligned(16))) char tail_a[tail::kBytesA];
-    __shared__ __attribute__((aligned(16))) char tail_b[tail::kBytesB];
-    tail::finish(L, S, angles, out, a, lmax, lnan, tail_a, tail_b);
-  }
-  if (BEST) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double os = __shfl_down(bs, o, 64);
-      const int64_t of = __shfl_down(bf, o, 64);
-      if (dev::better(os, of, bs, bf)) {
-        bs = os;
-        bf = of;
-      }
-    }
-    if (lane == 0) partials[(int64_t)win * L.blocks_per_scan + a] = BestPartial{bs, bf};
-  }
+  // the fused finish's LDS: this kernel has none of its own (unused, so not
+  // allocated, in best mode)
+  __shared__ __attribute__((aligned(16))) char tail_a[tail::kBytesA];
+  __shared__ __attribute__((aligned(16))) char tail_b[tail::kBytesB];
+  sink.done(L, S, angles, out, a, partials + (int64_t)win * L.blocks_per_scan + a, tail_a, tail_b);
 }
 
 template <int NS>
