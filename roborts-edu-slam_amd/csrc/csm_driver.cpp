@@ -1037,16 +1037,10 @@ int csm_load_scans_async(csm_ctx* c, int32_t n_scans, const double* pts, const i
   if ((st = check_offsets(c, n_scans, offsets)) != CSM_OK) return st;
   const int64_t n_total = n_scans > 0 ? offsets[n_scans] - offsets[0] : 0;
   if ((st = check_points(c, pts, n_total)) != CSM_OK) return st;
-  if (c->staged_count == 2) return c->fail(CSM_ERR_INVALID_ARG, "two batches already queued (csm_load_scans_async)");
+  csm_ctx::Staged* slot = nullptr;
+  if ((st = open_stage_slot(c, &slot)) != CSM_OK) return st;
+  csm_ctx::Staged& S = *slot;
   hipError_t e;
-  if (!c->stage_stream && (e = hipStreamCreateWithFlags(&c->stage_stream, hipStreamNonBlocking)) != hipSuccess)
-    return c->hip_fail(e, "hipStreamCreate(stage)");
-  csm_ctx::Staged& S = c->staged[(c->staged_head + c->staged_count) % 2];
-  if (!S.ready && (e = hipEventCreateWithFlags(&S.ready, hipEventDisableTiming)) != hipSuccess)
-    return c->hip_fail(e, "hipEventCreate(stage)");
-  if (!S.maxabs_h && (e = hipHostMalloc((void**)&S.maxabs_h, sizeof(unsigned long long), hipHostMallocDefault)) !=
-                         hipSuccess)
-    return c->hip_fail(e, "hipHostMalloc(stage)");
   const size_t bytes = (size_t)std::max<int64_t>(n_total, 1) * 2 * sizeof(double);
   if ((e = S.pts.ensure(bytes)) != hipSuccess || (e = S.maxabs_dev.ensure(sizeof(unsigned long long))) != hipSuccess)
     return c->hip_fail(e, "hipMalloc(stage)");
@@ -1057,7 +1051,7 @@ int csm_load_scans_async(csm_ctx* c, int32_t n_scans, const double* pts, const i
                                           hipMemcpyHostToDevice, c->stage_stream)) != hipSuccess) ||
       (e = csm::launch_points_maxabs((const double*)S.pts.p, n_total, (unsigned long long*)S.maxabs_dev.p,
                                      c->stage_stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(S.maxabs_h, S.maxabs_dev.p, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+      (e = hipMemcpyAsync(S.maxabs_h.p, S.maxabs_dev.p, sizeof(unsigned long long), hipMemcpyDeviceToHost,
                           c->stage_stream)) != hipSuccess ||
       (e = hipEventRecord(S.ready, c->stage_stream)) != hipSuccess)
     return c->hip_fail(e, "csm_load_scans_async");
@@ -1080,6 +1074,21 @@ int csm_host_free(void* p) { return (!p || hipHostFree(p) == hipSuccess) ? CSM_O
 }  // extern "C"
 
 namespace csmh {
+// The staging slot the next queued batch goes into (csm_load_scans_async,
+// csm_load_ranges*): a third queued batch is refused; the stage stream, the
+// slot's event and its pinned word are made by the first call that needs them.
+int open_stage_slot(csm_ctx* c, csm_ctx::Staged** out) {
+  if (c->staged_count == 2) return c->fail(CSM_ERR_INVALID_ARG, "two batches already queued (csm_load_scans_async)");
+  hipError_t e;
+  if ((e = c->stage_stream.create(hipStreamNonBlocking)) != hipSuccess) return c->hip_fail(e, "hipStreamCreate(stage)");
+  csm_ctx::Staged& S = c->staged[(c->staged_head + c->staged_count) % 2];
+  if ((e = S.ready.create(hipEventDisableTiming)) != hipSuccess) return c->hip_fail(e, "hipEventCreate(stage)");
+  if ((e = S.maxabs_h.ensure_exact(sizeof(unsigned long long))) != hipSuccess)
+    return c->hip_fail(e, "hipHostMalloc(stage)");
+  *out = &S;
+  return CSM_OK;
+}
+
 // The oldest queued batch (csm_load_scans_async) becomes the loaded one.
 int take_staged(csm_ctx* c) {
   if (c->staged_count <= 0) return CSM_OK;
@@ -1098,7 +1107,7 @@ int take_staged(csm_ctx* c) {
   c->loaded_n = S.n;
   c->loaded_grid.clear();
   double m;
-  std::memcpy(&m, S.maxabs_h, sizeof(m));
+  std::memcpy(&m, S.maxabs_h.p, sizeof(m));
   c->pts_maxabs = m;
   c->pts_cached = false;
   c->staged_head = (c->staged_head + 1) % 2;

@@ -87,25 +87,18 @@ void release_map_reader(csm_ctx* c) {
 // the least recently used slot). Returns true when the grid was found.
 bool select_grid(csm_ctx* c, const void* cells) {
   release_map_reader(c);
-  c->cur_use = ++c->grid_clock;
+  c->last_use = ++c->grid_clock;
   if (c->owns_host_grid() && c->key_cells == cells) return true;
   for (auto& g : c->parked)
     if (g.has_grid && g.key_cells == cells) {
-      if (c->owns_host_grid()) {
-        c->swap_grid(g);
-      } else {  // a borrowed or empty current grid is not kept
-        csm_ctx::GridSlot tmp;
-        c->swap_grid(tmp);
-        c->swap_grid(g);
-        std::swap(g, tmp);
-        tmp.grid_buf.release();
-        tmp.gridi.release();
-      }
-      c->cur_use = ++c->grid_clock;
+      // (a current grid that is no host map's own goes to the slot as well,
+      // buffers and all: the slot is reused like any other)
+      c->swap_grid(g);
+      c->last_use = ++c->grid_clock;
       return true;
     }
   if (c->owns_host_grid()) {
-    csm_ctx::GridSlot* v = &c->parked[0];
+    GridState* v = &c->parked[0];
     for (auto& g : c->parked) {
       if (!g.has_grid) {
         v = &g;
@@ -113,11 +106,9 @@ bool select_grid(csm_ctx* c, const void* cells) {
       }
       if (g.last_use < v->last_use) v = &g;
     }
-    v->grid_buf.release();
-    v->gridi.release();
-    *v = csm_ctx::GridSlot();
+    *v = GridState();  // the evicted grid's buffers are freed here
     c->swap_grid(*v);  // the current grid is parked; the empty slot becomes current
-    c->cur_use = ++c->grid_clock;
+    c->last_use = ++c->grid_clock;
   }
   c->has_grid = false;
   c->key_cells = nullptr;

@@ -28,6 +28,7 @@
 #include "csm_gridmap.h"
 #include "csm_gridmap_internal.hpp"
 #include "csm_internal.hpp"
+#include "csm_resources.hpp"
 #include "host_math.hpp"
 
 namespace {
@@ -35,30 +36,9 @@ namespace {
 using csm::GmCells;
 using csm::GmEnd;
 using csm::GmOps;
+using csmh::DevBuf;
 
 constexpr float kDefaultCellProb = 0.5f;  // grid_map_cell.h:30
-
-struct DBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    const size_t want = csm::grow_bytes(bytes, cap);
-    release();
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
 
 struct Box {  // BoundBox<double> (util/boundbox.h:35-143); default max FLT_MIN
   double minx = (double)FLT_MAX, miny = (double)FLT_MAX;
@@ -95,10 +75,10 @@ inline void pose_apply(double c, double s, double tx, double ty, double px, doub
 
 struct csm_gridmap {
   int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ready = nullptr;       // after the last enqueued update
-  hipEvent_t staged = nullptr;      // the last H2D copy out of h_ends has been consumed
-  hipEvent_t read_done = nullptr;   // reader streams' work so far (wait_readers)
+  csmh::Stream stream;     // declared before the buffers and events: destroyed after them
+  csmh::Event ready;       // after the last enqueued update
+  csmh::Event staged;      // the last H2D copy out of h_ends has been consumed
+  csmh::Event read_done;   // reader streams' work so far (wait_readers)
   std::mutex mu;
   std::string err;
 
@@ -122,11 +102,11 @@ struct csm_gridmap {
   GmOps ops{};
   uint32_t seq = 0;  // scans drawn with lines (line event keys)
 
-  DBuf prob, pass, hit, uidx, touched, fkey, oseq, ends, ktab, count;
+  DevBuf prob, pass, hit, uidx, touched, fkey, oseq, ends, ktab, count;
   // Fixed-point mirror of prob for the scan matcher (gridmap_fixed_point):
   // kept equal to (prob - fpm_outside) * 2^fpm_exp by every kernel that writes
   // prob while fpm_valid; a growth or an incompatible value drops it.
-  DBuf fpm;
+  DevBuf fpm;
   bool fpm_valid = false;
   float fpm_outside = 0.f;
   int fpm_exp = 0;
@@ -137,8 +117,7 @@ struct csm_gridmap {
   bool vals_known = true;
   int vals_min_g = INT32_MAX;  // every nonzero value is a multiple of 2^vals_min_g
   float vals_max = 0.f;        // max |value|
-  void* h_ends = nullptr;
-  size_t h_cap = 0;
+  csmh::HostBuf h_ends;  // pinned staging of the endpoints (upload_ends)
   bool ktab_dirty = true;
   std::vector<GmEnd> pending;  // blur endpoints not yet drawn (order-free, batched)
 
@@ -222,7 +201,7 @@ struct DeviceGuard {
     if (e_ != hipSuccess) return m->hip_fail(e_, #expr); \
   } while (0)
 
-int alloc_cells(csm_gridmap* m, int64_t n, DBuf& p, DBuf& ps, DBuf& h, DBuf& u, DBuf& t) {
+int alloc_cells(csm_gridmap* m, int64_t n, DevBuf& p, DevBuf& ps, DevBuf& h, DevBuf& u, DevBuf& t) {
   GM_HIP(p.ensure((size_t)n * 4));
   if (m->kind == csm::kGmCount) {
     GM_HIP(ps.ensure((size_t)n * 4));
@@ -238,20 +217,13 @@ int upload_ends(csm_gridmap* m, const std::vector<GmEnd>& v) {
   if (v.empty()) return CSM_OK;
   const size_t bytes = v.size() * sizeof(GmEnd);
   GM_HIP(hipEventSynchronize(m->staged));
-  if (bytes > m->h_cap) {
-    const size_t want = csm::grow_bytes(bytes, m->h_cap);
-    if (m->h_ends) (void)hipHostFree(m->h_ends);
-    m->h_ends = nullptr;
-    m->h_cap = 0;
-    GM_HIP(hipHostMalloc(&m->h_ends, want, hipHostMallocDefault));
-    m->h_cap = want;
-  }
+  GM_HIP(m->h_ends.ensure(bytes));
   if (bytes > m->ends.cap) {
     GM_HIP(hipStreamSynchronize(m->stream));  // the old buffer may still be read
     GM_HIP(m->ends.ensure(bytes));
   }
-  std::memcpy(m->h_ends, v.data(), bytes);
-  GM_HIP(hipMemcpyAsync(m->ends.p, m->h_ends, bytes, hipMemcpyHostToDevice, m->stream));
+  std::memcpy(m->h_ends.p, v.data(), bytes);
+  GM_HIP(hipMemcpyAsync(m->ends.p, m->h_ends.p, bytes, hipMemcpyHostToDevice, m->stream));
   GM_HIP(hipEventRecord(m->staged, m->stream));
   return CSM_OK;
 }
@@ -306,7 +278,7 @@ int extend_size(csm_gridmap* m) {
   const int64_t n = (int64_t)nsx * nsy;
   if (nsx <= 0 || nsy <= 0 || n >= ((int64_t)1 << 31))
     return m->fail(CSM_ERR_ALLOC, "map growth beyond 2^31 cells");
-  DBuf np, nps, nh, nu, nt;
+  DevBuf np, nps, nh, nu, nt;  // the grown arrays; after the swap below, the old ones (freed on return)
   if ((st = alloc_cells(m, n, np, nps, nh, nu, nt)) != CSM_OK) return st;
   GmCells N;
   N.prob = np.as<float>();
@@ -332,11 +304,6 @@ int extend_size(csm_gridmap* m) {
   std::swap(m->hit, nh);
   std::swap(m->uidx, nu);
   std::swap(m->touched, nt);
-  np.release();
-  nps.release();
-  nh.release();
-  nu.release();
-  nt.release();
   m->fkey.release();  // per-scan line scratch: rebuilt at the new size
   m->oseq.release();
   m->off_x -= fx / m->scale_factor;
@@ -620,10 +587,9 @@ int csm_gridmap_create(int device, int32_t kind, double resolution, int32_t size
   auto* m = new csm_gridmap();
   m->device = device;
   DeviceGuard g(device);
-  if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&m->ready, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&m->read_done, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&m->staged, hipEventDisableTiming) != hipSuccess) {
+  if (m->stream.create(hipStreamNonBlocking) != hipSuccess || m->ready.create(hipEventDisableTiming) != hipSuccess ||
+      m->read_done.create(hipEventDisableTiming) != hipSuccess ||
+      m->staged.create(hipEventDisableTiming) != hipSuccess) {
     csm_gridmap_destroy(m);
     return CSM_ERR_HIP;
   }
@@ -671,26 +637,16 @@ int csm_gridmap_create(int device, int32_t kind, double resolution, int32_t size
 
 int csm_gridmap_destroy(csm_gridmap* m) {
   if (!m) return CSM_OK;
+  DeviceGuard g(m->device);  // across the delete: the map's members free themselves on its device
+  if (m->stream) (void)hipStreamSynchronize(m->stream);
   {
-    DeviceGuard g(m->device);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
-    for (DBuf* b : {&m->prob, &m->pass, &m->hit, &m->uidx, &m->touched, &m->fkey, &m->oseq, &m->ends, &m->ktab,
-                    &m->count, &m->fpm})
-      b->release();
-    if (m->h_ends) (void)hipHostFree(m->h_ends);
-    {
-      std::lock_guard<std::mutex> lk(g_readers_mu);
-      g_readers.erase(m);
-      auto f = g_fences.find(m);
-      if (f != g_fences.end()) {
-        for (hipEvent_t ev : f->second) (void)hipEventDestroy(ev);
-        g_fences.erase(f);
-      }
+    std::lock_guard<std::mutex> lk(g_readers_mu);
+    g_readers.erase(m);
+    auto f = g_fences.find(m);
+    if (f != g_fences.end()) {
+      for (hipEvent_t ev : f->second) (void)hipEventDestroy(ev);
+      g_fences.erase(f);
     }
-    if (m->ready) (void)hipEventDestroy(m->ready);
-    if (m->staged) (void)hipEventDestroy(m->staged);
-    if (m->read_done) (void)hipEventDestroy(m->read_done);
-    if (m->stream) (void)hipStreamDestroy(m->stream);
   }
   delete m;
   return CSM_OK;

@@ -11,6 +11,13 @@
 //                        the FAST (branch-and-bound) replay
 //   csm_optimize_host.cpp the Gauss-Newton matcher's host loop
 //
+// Ownership is a property of the types (csm_resources.hpp): every buffer,
+// event and stream of the context frees itself, so csm_destroy only drains
+// and deletes. What one part of a batch needs per launch is LaunchSlot, what a
+// resident grid is GridState; the context is one of each (its bases) and holds
+// the others in alt[] and parked[], exchanged whole by swap_slot / swap_grid:
+// a field added to either struct is swapped, parked and freed with it.
+//
 // Compiled with g++ -O2 -ffp-contract=off (no -march), like the reference's
 // Release build, so every host double expression rounds as the reference's
 // does. The candidate sort is libstdc++'s std::sort on records compared by
@@ -24,6 +31,7 @@
 #include "csm_finish_rules.hpp"
 #include "csm_gridmap.h"
 #include "csm_gridmap_internal.hpp"
+#include "csm_resources.hpp"
 #include "host_math.hpp"
 #include "csm_pyramid.hpp"
 #include "csm_level_decision.hpp"
@@ -92,47 +100,6 @@ struct Geometry {
     out[0] = inv_a * p[0] + ntx;
     out[1] = inv_a * p[1] + nty;
     out[2] = p[2];
-  }
-};
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    const size_t want = csm::grow_bytes(bytes, cap);
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
-struct HostBuf {  // pinned staging for device->host score copies
-  void* p = nullptr;
-  size_t cap = 0;
-  // flags: hipHostMallocCoherent for buffers kernels write straight into
-  hipError_t ensure(size_t bytes, unsigned flags = hipHostMallocDefault) {
-    if (bytes <= cap) return hipSuccess;
-    const size_t want = csm::grow_bytes(bytes, cap);
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipHostMalloc(&p, want, flags);
-    if (e == hipSuccess) cap = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
   }
 };
 
@@ -369,21 +336,97 @@ struct PendingRun {
   bool defer_timing = false;
 };
 
-}  // namespace csmh
-
-struct csm_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;  // kernels
+// The context's streams: its first base, so they are destroyed last, after
+// every buffer and event of the context (bases go after members, in reverse).
+struct CtxStreams {
+  Stream stream;  // kernels
   // Per-launch copies run on their own streams (DMA engines), ordered against
   // the kernels by events: a part's inputs go up while the other part's
   // kernels run, its results come down while the next kernels run.
-  hipStream_t h2d = nullptr, d2h = nullptr;
+  Stream h2d, d2h;
   // The exact finish pass (a few latency-bound blocks per launch: the flagged
   // windows' sort chains) runs here, after the fast pass (ev_fast), so it
   // overlaps the other part's scoring on `stream`; the part's results go down
   // after it (ev_k on this stream).
-  hipStream_t x_stream = nullptr;
-  hipEvent_t ev_fast = nullptr;
+  Stream x_stream;
+  Stream stage_stream;  // queued batches' uploads (csm_ctx::Staged), made by the first one
+};
+
+// The per-launch set of one part of a batch: the context is one (the current
+// part's) and keeps the others in csm_ctx::alt; swap_slot exchanges them whole.
+// What a part needs per launch is declared here and nowhere else.
+struct LaunchSlot {
+  DevBuf scans, angles, scores, partials, best, fin;
+  DevBuf ang_max;  // the fused fast finish: per (window, angle) max score (csm_tail.hpp)
+  DevBuf win_ctr;  // ... and per window the waves arrived (zero between launches)
+  HostBuf h_scores, h_fin, h_angles, h_sw;
+  HostBuf h_angles_next;  // the next level's angle rows while this level's are still read (level_end_begin)
+  // Host-signal device finish of the throughput path (CSM_HOST_SIGNAL=0: off):
+  // the finish writes FinishOut straight into coherent pinned memory and the
+  // pass that ends last stores a flag there (no D2H copy, no event round trip).
+  // fin_sig: done counter | need[nw] | list {count, tag, windows[nw]}; h_fin_sig: FinishOut[nw] | flag.
+  DevBuf fin_sig;
+  HostBuf h_fin_sig;
+  // per-kernel HIP-event timing (csm_set_profiling / csm_kernel_stats)
+  Event ev0, ev1, ev2;
+  Event ev_ft;  // profiling: the fast finish pass ended (timed; ev_fast is not)
+  // profiling a level scored in two spans (level_begin_split): the first span's
+  // end and the second's start, so the host's planning between them is not
+  // counted as kernel time
+  Event ev_g0, ev_g1;
+  Event ev_done;  // end of a launch's work (async runs)
+  Event ev_in;    // a launch's inputs are on the device
+  Event ev_k;     // a launch's kernels are done
+  Event ev_fast;  // the fast finish pass ended: the exact pass on x_stream waits for it
+  bool span_gap = false;
+  int32_t list_tag = 0;  // host signal: the tag of the slot's latest scoring call (run_windows)
+  // the fused finish: a level's first span is out but its last window's span
+  // is not (a level that failed on the host between them leaves level_ctr and
+  // the window counters part-counted; the slot's next tail level zeroes them)
+  bool tail_open = false;
+
+  hipError_t create_sync_events() {
+    hipError_t e = hipSuccess;
+    for (Event* ev : {&ev_done, &ev_in, &ev_k, &ev_fast})
+      if (e == hipSuccess) e = ev->create(hipEventDisableTiming);
+    return e;
+  }
+  hipError_t create_timing_events() {
+    hipError_t e = hipSuccess;
+    for (Event* ev : {&ev0, &ev1, &ev2, &ev_ft, &ev_g0, &ev_g1})
+      if (e == hipSuccess) e = ev->create(hipEventDefault);
+    return e;
+  }
+};
+
+// A resident grid: the context is one (the current grid) and parks others in
+// csm_ctx::parked; swap_grid exchanges them whole. The palette and the strip
+// copies are the context's, keyed on grid_gen, not part of this.
+struct GridState {
+  csm_map_info info{};
+  bool has_grid = false;
+  const float* d_grid = nullptr;  // owned (grid_buf) or borrowed
+  DevBuf grid_buf;
+  DevBuf gridi;  // exact fixed-point copy of the grid (ensure_int_grid)
+  const int32_t* d_gridi = nullptr;  // the current fixed-point grid: gridi, or a map's mirror (borrowed)
+  const void* key_cells = nullptr;
+  int64_t key_stride = 0, key_version = -1;
+  int32_t key_sx = -1, key_sy = -1;
+  bool int_checked = false, int_ok = false;
+  int int_exp = 0;
+  int32_t pitch = 0;    // gridi row pitch (cells)
+  int32_t n_grids = 1;  // grids resident back to back (csm_set_grid_stack)
+  int32_t outside_i = 0;
+  double int_max_abs = 0.0;  // max |cell| (and |outside|) for the per-launch exactness bound
+  uint64_t last_use = 0;     // csm_ctx::grid_clock when it was last selected
+};
+
+static_assert(kMoveOnly<LaunchSlot> && kMoveOnly<GridState>, "slots and grids are exchanged, never copied");
+
+}  // namespace csmh
+
+struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState {
+  int device = 0;
   // Signalled levels of the 3-level driver: the host completes (and plans the
   // next level of) the windows the fast pass settled while the exact pass
   // sorts the flagged ones (FinishArgs::host_fast_flag).
@@ -413,34 +456,16 @@ struct csm_ctx {
     pool->run(n, threads, std::forward<F>(fn));
   }
 
-  csm_map_info info{};
-  bool has_grid = false;
-  const float* d_grid = nullptr;  // owned (grid_buf) or borrowed
-  csmh::DevBuf grid_buf;
-  const void* key_cells = nullptr;
-  int64_t key_stride = 0, key_version = -1;
-  int32_t key_sx = -1, key_sy = -1;
-
-  csmh::DevBuf pts, scans, angles, scores, partials, best, fin;
-  csmh::DevBuf ang_max;  // the fused fast finish: per (window, angle) max score (csm_tail.hpp)
-  csmh::DevBuf win_ctr;  // ... and per window the waves arrived (zero between launches)
+  csmh::DevBuf pts;         // the resident batch's points (every part reads them)
   csmh::DevBuf best_tiles;  // tiled box mode: one best per (window, tile) between the two reductions
   csmh::HostBuf h_search;   // csm_search_windows: pinned staging of the points and angle table
   bool staging_dirty = false;  // a search failed with copies out of its staging possibly in flight
   csm_gridmap* reader_map = nullptr;  // the map csm_set_grid_gridmap borrowed (its updates wait for this stream)
   csmh::HostBuf h_pts;      // upload_points: pinned staging of a scan's points (and small host arrays)
-  hipEvent_t ev_pts = nullptr;  // the last copy out of h_pts
+  csmh::Event ev_pts;       // the last copy out of h_pts
   bool ev_pts_used = false;
-  csmh::HostBuf h_scores, h_fin, h_angles, h_sw;
-  csmh::HostBuf h_angles_next;  // the next level's angle rows while this level's are still read (level_end_begin)
-  // Host-signal device finish of the throughput path (CSM_HOST_SIGNAL=0: off):
-  // the finish writes FinishOut straight into coherent pinned memory and the
-  // pass that ends last stores a flag there (no D2H copy, no event round trip).
-  // fin_sig: done counter | need[nw] | list {count, tag, windows[nw]}; h_fin_sig: FinishOut[nw] | flag.
-  bool host_signal = true;
+  bool host_signal = true;  // the host-signal device finish (LaunchSlot::fin_sig; CSM_HOST_SIGNAL=0: off)
   double t_call = 0.0, t_exit = 0.0;  // profiling: the 3-level call's entry and the previous call's exit (now_ms)
-  csmh::DevBuf fin_sig;
-  csmh::HostBuf h_fin_sig;
   bool device_finish = true;  // CSM_FINISH=host forces the host std::sort path
   bool fast_finish = true;    // CSM_FINISH=exact: always the full device std::sort emulation
   int device_finish_min = 1;  // fewest windows per launch that finish on the device
@@ -477,7 +502,7 @@ struct csm_ctx {
   int split_target_blocks = 512;  // blocks a split launch aims for
   int fast_wide_windows = 0;      // fast finishes of <= this many windows on 1024 threads (0: 64)
   csmh::HostBuf h_pack;  // pinned staging of packed grid rows / cell updates (grid uploads)
-  hipEvent_t ev_pack = nullptr;  // the last copy out of h_pack (cell updates return before it ends)
+  csmh::Event ev_pack;   // the last copy out of h_pack (cell updates return before it ends)
   bool ev_pack_used = false;
   // the points last uploaded (upload_points skips an identical upload: the
   // reference's ScanMatchers calls each level with the same range data)
@@ -489,44 +514,11 @@ struct csm_ctx {
   // cells pointer (the map's identity); switching between maps (the front
   // end's fine map, the back end's maps) swaps the current grid with a parked
   // one instead of re-uploading it. The least recently used is evicted.
-  struct GridSlot {
-    csm_map_info info{};
-    bool has_grid = false;
-    const float* d_grid = nullptr;
-    csmh::DevBuf grid_buf, gridi;
-    const int32_t* d_gridi = nullptr;
-    const void* key_cells = nullptr;
-    int64_t key_stride = 0, key_version = -1;
-    int32_t key_sx = -1, key_sy = -1;
-    bool int_checked = false, int_ok = false;
-    int int_exp = 0;
-    int32_t pitch = 0, n_grids = 1, outside_i = 0;
-    double int_max_abs = 0.0;
-    uint64_t last_use = 0;
-  };
   static constexpr int kParkedGrids = 3;
-  GridSlot parked[kParkedGrids];
-  uint64_t grid_clock = 0, cur_use = 0;
-  void swap_grid(GridSlot& g) {
-    std::swap(info, g.info);
-    std::swap(has_grid, g.has_grid);
-    std::swap(d_grid, g.d_grid);
-    std::swap(grid_buf, g.grid_buf);
-    std::swap(gridi, g.gridi);
-    std::swap(d_gridi, g.d_gridi);
-    std::swap(key_cells, g.key_cells);
-    std::swap(key_stride, g.key_stride);
-    std::swap(key_version, g.key_version);
-    std::swap(key_sx, g.key_sx);
-    std::swap(key_sy, g.key_sy);
-    std::swap(int_checked, g.int_checked);
-    std::swap(int_ok, g.int_ok);
-    std::swap(int_exp, g.int_exp);
-    std::swap(pitch, g.pitch);
-    std::swap(n_grids, g.n_grids);
-    std::swap(outside_i, g.outside_i);
-    std::swap(int_max_abs, g.int_max_abs);
-    std::swap(cur_use, g.last_use);
+  csmh::GridState parked[kParkedGrids];
+  uint64_t grid_clock = 0;
+  void swap_grid(csmh::GridState& g) {
+    std::swap(static_cast<csmh::GridState&>(*this), g);
     grid_gen = ++gen_clock;
   }
   // The current grid is a host map's own copy (worth keeping when another
@@ -539,22 +531,13 @@ struct csm_ctx {
   csmh::DevBuf opt_off, opt_scans, opt_sums;
   csmh::HostBuf h_opt_scans, h_opt_sums;
 
-  // exact fixed-point copy of the grid (ensure_int_grid)
-  csmh::DevBuf gridi, gstats;
-  const int32_t* d_gridi = nullptr;  // the current fixed-point grid: gridi, or a map's mirror (borrowed)
+  csmh::DevBuf gstats;  // ensure_int_grid's whole-grid statistics
   // Changes whenever the current fixed-point grid may have (rebuilt, cells or
   // rows refreshed, another grid swapped in): keys the pooled levels of the
   // multi-resolution search.
   uint64_t grid_gen = 0, gen_clock = 0;
   csm::PyramidSearch pyramid;
-  bool int_checked = false, int_ok = false;
-  int int_exp = 0;
-  int32_t pitch = 0;  // gridi row pitch (cells)
-  int32_t n_grids = 1;  // grids resident back to back (csm_set_grid_stack)
-  double int_max_abs = 0.0;  // max |cell| (and |outside|) for the per-launch exactness bound
-  int32_t outside_i = 0;
   double pts_maxabs = 0.0;   // max |x|+|y| of the resident points (NaN: unbounded)
-
 
   // Batches queued by csm_load_scans_async: uploaded on stage_stream (not on
   // h2d, whose per-launch input copies would queue behind a batch), their
@@ -564,8 +547,8 @@ struct csm_ctx {
     csmh::DevBuf pts, maxabs_dev;
     std::vector<int64_t> off;
     int32_t n = -1;
-    hipEvent_t ready = nullptr;
-    unsigned long long* maxabs_h = nullptr;  // pinned
+    csmh::Event ready;
+    csmh::HostBuf maxabs_h;  // pinned: the 8 bytes of maxabs_dev, copied down before `ready`
     // a batch queued as raw ranges (csm_load_ranges*): the ranges as uploaded,
     // the kept beams per scan, their prefix sums, and those copied to pinned
     // memory before `ready` (take_staged reads them where it reads maxabs_h)
@@ -573,7 +556,6 @@ struct csm_ctx {
     csmh::HostBuf off_h;
     bool from_ranges = false;
   };
-  hipStream_t stage_stream = nullptr;
   Staged staged[2];
   int staged_head = 0, staged_count = 0;
   // The laser's per-beam (cos a_i, sin a_i) on the device (csm_ranges.cpp),
@@ -594,40 +576,22 @@ struct csm_ctx {
   bool profiling = false;
   bool profile_first_level = false;  // csm_set_profiling(ctx, 2): the 3-level driver times its first level only
   bool stats_dump = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-  hipEvent_t ev_ft = nullptr;    // profiling: the fast finish pass ended (timed; ev_fast is not)
-  // profiling a level scored in two spans (level_begin_split): the first span's
-  // end and the second's start, so the host's planning between them is not
-  // counted as kernel time
-  hipEvent_t ev_g0 = nullptr, ev_g1 = nullptr;
-  bool span_gap = false;
-  int32_t list_tag = 0;  // host signal: the tag of the slot's latest scoring call (run_windows)
-  // the fused finish: a level's first span is out but its last window's span
-  // is not (a level that failed on the host between them leaves level_ctr and
-  // the window counters part-counted; the slot's next tail level zeroes them)
-  bool tail_open = false;
-  hipEvent_t ev_done = nullptr;  // end of a launch's work (async runs)
-  hipEvent_t ev_in = nullptr;    // a launch's inputs are on the device
-  hipEvent_t ev_k = nullptr;     // a launch's kernels are done
 
-  // Second set of per-launch buffers: the 3-level driver keeps two halves of
+  // The other parts' per-launch sets: the 3-level driver keeps two halves of
   // a batch in flight (match_levels_pipelined); swap_slot() exchanges the
   // sets so run_windows works on whichever half is current. Every part uses
   // the one kernel stream: a stream per part measured slower (two concurrent
   // box-kernel launches contend for L2, 1.01 -> 1.57 ms each; profiles/r01).
-  struct Slot {
-    csmh::DevBuf scans, angles, scores, partials, best, fin, ang_max, win_ctr;
-    csmh::HostBuf h_scores, h_fin, h_angles, h_sw, h_angles_next, h_fin_sig;
-    csmh::DevBuf fin_sig;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev_done = nullptr, ev_in = nullptr, ev_k = nullptr;
-    hipEvent_t ev_ft = nullptr, ev_g0 = nullptr, ev_g1 = nullptr;
-    hipEvent_t ev_fast = nullptr;
-    bool span_gap = false;
-    int32_t list_tag = 0;
-    bool tail_open = false;
-  };
   static constexpr int kMaxParts = 4;
-  Slot alt[kMaxParts - 1];
+  csmh::LaunchSlot alt[kMaxParts - 1];
+  // the context's own set, then alt[]: fn(LaunchSlot&) until one fails
+  template <class F>
+  hipError_t each_slot(F&& fn) {
+    hipError_t e = fn(static_cast<csmh::LaunchSlot&>(*this));
+    for (auto& a : alt)
+      if (e == hipSuccess) e = fn(a);
+    return e;
+  }
   int pipeline_min = 512;    // fewest scans the 3-level driver splits into parts (CSM_PIPELINE)
   bool skip_dead_lists = true;  // live_lists (CSM_SKIP_DEAD_LISTS=0: every level fills both lists)
   int pipeline_parts = 2;    // parts in flight (CSM_PIPELINE_PARTS: 2..kMaxParts; 2 measured fastest)
@@ -650,36 +614,8 @@ struct csm_ctx {
                              // r04 A/B, 2 runs each: 500 9.40, 550 9.61, 600 9.56, 650 9.47 G scorings/s)
   int part0_permille_submit = 500;  // ... for submitted batches (r04 A/B with
                                     // the deferred hand-off: 500 10.45 / 10.48, 550 10.39 / 10.41 G)
-  void swap_slot(int i) {    // i >= 1: exchange the current buffer set with alt[i - 1]
-    Slot& a = alt[i - 1];
-    std::swap(scans, a.scans);
-    std::swap(angles, a.angles);
-    std::swap(scores, a.scores);
-    std::swap(partials, a.partials);
-    std::swap(best, a.best);
-    std::swap(fin, a.fin);
-    std::swap(ang_max, a.ang_max);
-    std::swap(win_ctr, a.win_ctr);
-    std::swap(h_scores, a.h_scores);
-    std::swap(h_fin, a.h_fin);
-    std::swap(h_angles, a.h_angles);
-    std::swap(h_angles_next, a.h_angles_next);
-    std::swap(h_fin_sig, a.h_fin_sig);
-    std::swap(fin_sig, a.fin_sig);
-    std::swap(h_sw, a.h_sw);
-    std::swap(ev0, a.ev0);
-    std::swap(ev1, a.ev1);
-    std::swap(ev2, a.ev2);
-    std::swap(ev_done, a.ev_done);
-    std::swap(ev_in, a.ev_in);
-    std::swap(ev_k, a.ev_k);
-    std::swap(ev_fast, a.ev_fast);
-    std::swap(ev_ft, a.ev_ft);
-    std::swap(ev_g0, a.ev_g0);
-    std::swap(ev_g1, a.ev_g1);
-    std::swap(span_gap, a.span_gap);
-    std::swap(list_tag, a.list_tag);
-    std::swap(tail_open, a.tail_open);
+  void swap_slot(int i) {    // i >= 1: exchange the current per-launch set with alt[i - 1]
+    std::swap(static_cast<csmh::LaunchSlot&>(*this), alt[i - 1]);
   }
   // profiling: the pool's last job, as "pool:<what>" (total_ms = the first
   // worker's join latency, algorithmic_bytes = the caller's share of the items)
@@ -835,6 +771,7 @@ inline bool map_ready(const csm_ctx* c) { return c->has_grid && c->info.update_i
 // point but csm_scan_matchers_submit calls it first); the state's release
 int pipe_drain(csm_ctx* c);
 void pipe_free(csm_ctx* c);
+int open_stage_slot(csm_ctx* c, csm_ctx::Staged** out);
 int take_staged(csm_ctx* c);
 int drop_staged(csm_ctx* c);
 int matchers_loaded_locked(csm_ctx* c, const csm_param levels[3], int32_t use_fine, double* poses, double* covs,

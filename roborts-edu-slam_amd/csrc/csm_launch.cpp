@@ -945,7 +945,7 @@ void Launch::fill_pending(const char* kname, PendingRun& p) {
   p.n_flags = n_flags;
   p.device_finish = mode == Finish::kDevice && time_fin();
   // (with the fused finish the fast interval is empty: the scoring time holds it)
-  p.ev_fast = (time_fin() && mode == Finish::kDevice && c->fast_finish && c->x_stream) ? c->ev_ft : nullptr;
+  p.ev_fast = (time_fin() && mode == Finish::kDevice && c->fast_finish && c->x_stream) ? (hipEvent_t)c->ev_ft : nullptr;
   if (c->span_gap) {
     p.gap0 = c->ev_g0;
     p.gap1 = c->ev_g1;

@@ -52,16 +52,12 @@ int ensure_laser_table(csm_ctx* c, const csm_laser& L) {
 // Profiling (csm_set_profiling 1): HIP-event times of the three ingest
 // kernels of one batch, waited for here (the call is synchronous then).
 struct IngestTimer {
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  Event ev[4];
   bool on = false;
   explicit IngestTimer(bool want) {
     on = want;
     for (int i = 0; on && i < 4; ++i)
-      if (hipEventCreate(&ev[i]) != hipSuccess) on = false;
-  }
-  ~IngestTimer() {
-    for (auto e : ev)
-      if (e) (void)hipEventDestroy(e);
+      if (ev[i].create(hipEventDefault) != hipSuccess) on = false;
   }
   void mark(int i, hipStream_t s) {
     if (on && hipEventRecord(ev[i], s) != hipSuccess) on = false;
@@ -88,17 +84,11 @@ int queue_ranges(csm_ctx* c, const csm_laser* laser, int32_t n_scans, const floa
   if (!csm::laser_threshold(L, &threshold))
     return c->fail(CSM_ERR_INVALID_ARG, "bad laser (n_beams <= 0, range_min >= range_max or a field not finite)");
   if (n_scans < 0 || (n_scans > 0 && !ranges)) return c->fail(CSM_ERR_INVALID_ARG, "bad ranges");
-  if (c->staged_count == 2) return c->fail(CSM_ERR_INVALID_ARG, "two batches already queued (csm_load_scans_async)");
-  hipError_t e;
-  if (!c->stage_stream && (e = hipStreamCreateWithFlags(&c->stage_stream, hipStreamNonBlocking)) != hipSuccess)
-    return c->hip_fail(e, "hipStreamCreate(stage)");
-  csm_ctx::Staged& S = c->staged[(c->staged_head + c->staged_count) % 2];
-  if (!S.ready && (e = hipEventCreateWithFlags(&S.ready, hipEventDisableTiming)) != hipSuccess)
-    return c->hip_fail(e, "hipEventCreate(stage)");
-  if (!S.maxabs_h && (e = hipHostMalloc((void**)&S.maxabs_h, sizeof(unsigned long long), hipHostMallocDefault)) !=
-                         hipSuccess)
-    return c->hip_fail(e, "hipHostMalloc(stage)");
   int st;
+  csm_ctx::Staged* slot = nullptr;
+  if ((st = open_stage_slot(c, &slot)) != CSM_OK) return st;
+  csm_ctx::Staged& S = *slot;
+  hipError_t e;
   if ((st = ensure_laser_table(c, L)) != CSM_OK) return st;
   const int64_t n_ranges = (int64_t)n_scans * L.n_beams;  // the most points the batch can keep
   const size_t range_bytes = (size_t)n_ranges * sizeof(float);
@@ -136,7 +126,7 @@ int queue_ranges(csm_ctx* c, const csm_laser* laser, int32_t n_scans, const floa
   tm.mark(3, s);
   if ((e = csm::launch_points_maxabs((const double*)S.pts.p, n_ranges, (unsigned long long*)S.maxabs_dev.p, s)) !=
           hipSuccess ||
-      (e = hipMemcpyAsync(S.maxabs_h, S.maxabs_dev.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s)) !=
+      (e = hipMemcpyAsync(S.maxabs_h.p, S.maxabs_dev.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s)) !=
           hipSuccess ||
       (e = hipMemcpyAsync(S.off_h.p, S.off_dev.p, off_bytes, hipMemcpyDeviceToHost, s)) != hipSuccess ||
       (e = hipEventRecord(S.ready, s)) != hipSuccess)

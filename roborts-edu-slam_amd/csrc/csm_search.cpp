@@ -14,6 +14,7 @@
 // (depth-first over slices, level-synchronous inside one), so memory stays
 // fixed whatever the pruning rate.
 #include "csm_pyramid.hpp"
+#include "csm_resources.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -26,25 +27,8 @@ namespace csm {
 
 namespace {
 
-struct Buf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  ~Buf() { release(); }
-};
+// every buffer here is sized exactly (ensure_exact): the levels are gigabytes
+using csmh::DevBuf;
 
 double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -54,19 +38,19 @@ double now_ms() {
 
 struct PyramidSearch::Impl {
   // pooled levels 1..kPyrMaxDepth of the current fixed-point grid
-  Buf level[kPyrMaxDepth + 1];
+  DevBuf level[kPyrMaxDepth + 1];
   PyrGrid lev[kPyrMaxDepth + 1]{};
   const void* key_g = nullptr;
   uint64_t key_gen = 0;
   int32_t key_sx = -1, key_sy = -1, key_grids = -1, built = 0;
   // the top level's box copy (pyr_topbox_kernel): depth and pieces it was built for
-  Buf box;
+  DevBuf box;
   PyrGrid boxg{};
   int32_t box_depth = -1, box_npc = 0;
   // per-depth node lists, their values and counts (counts[d]: nodes[d]'s
   // length as the expand that filled it left it)
-  Buf nodes[kPyrMaxDepth + 1], vals[kPyrMaxDepth + 1];
-  Buf partials, probe_slot, probe_nodes, probe_vals;
+  DevBuf nodes[kPyrMaxDepth + 1], vals[kPyrMaxDepth + 1];
+  DevBuf partials, probe_slot, probe_nodes, probe_vals;
   // device state of a search, set by one init launch: the incumbent, the
   // nodes scored per depth, and a pool of list counters (each expand appends
   // to a fresh, already zero counter: no memset per level). Once the fresh
@@ -75,25 +59,26 @@ struct PyramidSearch::Impl {
   // parent list (depth d + 1) whose count that expand reads.
   static constexpr int kCountPool = 64;
   static constexpr int kCountSlots = kCountPool + kPyrMaxDepth + 1;
-  Buf state;  // BestPartial inc | scored[kPyrMaxDepth + 1] | pool[kCountSlots]
+  DevBuf state;  // BestPartial inc | scored[kPyrMaxDepth + 1] | pool[kCountSlots]
   int cslot[kPyrMaxDepth + 1] = {};  // pool slot of list d's count (slot 0: never written, zero)
   int next_slot = 1;
   BestPartial* inc_dev() const { return (BestPartial*)state.p; }
   unsigned long long* scored_dev() const { return (unsigned long long*)((char*)state.p + sizeof(BestPartial)); }
   unsigned long long* pool_dev() const { return scored_dev() + kPyrMaxDepth + 1; }
   // the beam-box top level: integer sums of the implicit node list
-  Buf top_sums, top_thr, top_slab;
+  DevBuf top_sums, top_thr, top_slab;
   int top_implicit = -1;  // its depth while a search runs (-1: the top is a node list)
   int32_t top_nj = 0;
   // pinned: two counts read back, then the state's incumbent and scored
   // counts (pageable copies wait for the device: ~20-70 us each)
-  unsigned long long* h_counts = nullptr;
-  BestPartial* h_inc() const { return (BestPartial*)(h_counts + 2); }
+  csmh::HostBuf h_words;
+  unsigned long long* h_counts() const { return h_words.as<unsigned long long>(); }
+  BestPartial* h_inc() const { return (BestPartial*)(h_counts() + 2); }
   unsigned long long* h_scored() const { return (unsigned long long*)(h_inc() + 1); }
-  hipEvent_t ev_top[2] = {nullptr, nullptr};  // PyrInputs::timed
+  csmh::Event ev_top[2];  // PyrInputs::timed
   // PyrInputs::timed: an event pair around each bound launch (depth, pair)
   static constexpr int kBoundEvents = 256;
-  std::vector<hipEvent_t> ev_bound;
+  std::vector<csmh::Event> ev_bound;
   std::vector<int> ev_bound_depth;
   int n_ev_bound = 0;
   int64_t cap = (int64_t)1 << 25;
@@ -116,16 +101,9 @@ struct PyramidSearch::Impl {
   PyrInputs in{};
   PyrStats* st = nullptr;
 
-  ~Impl() {
-    if (h_counts) (void)hipHostFree(h_counts);
-    for (hipEvent_t e : ev_top)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ev_bound)
-      if (e) (void)hipEventDestroy(e);
-  }
   hipError_t mark_top(int i, hipStream_t stream) {
     hipError_t e;
-    if (!ev_top[i] && (e = hipEventCreate(&ev_top[i])) != hipSuccess) return e;
+    if ((e = ev_top[i].create(hipEventDefault)) != hipSuccess) return e;
     return hipEventRecord(ev_top[i], stream);
   }
 
@@ -154,7 +132,7 @@ struct PyramidSearch::Impl {
       L.pitch = ((L.q << d) + 3) & ~3;
       L.stride = (int64_t)L.pitch * L.height;
       L.qs = kPyrQuant;
-      if ((e = level[d].ensure((size_t)L.stride * (size_t)x.n_grids * sizeof(int16_t))) != hipSuccess) return e;
+      if ((e = level[d].ensure_exact((size_t)L.stride * (size_t)x.n_grids * sizeof(int16_t))) != hipSuccess) return e;
       L.g = level[d].p;
       if ((e = launch_pyr_pool(lev[d - 1], L, d, x.n_grids, x.stream)) != hipSuccess) return e;
     }
@@ -179,7 +157,7 @@ struct PyramidSearch::Impl {
     if (b.stride * 2 >= INT32_MAX) return hipErrorInvalidValue;
     hipError_t e;
     const double t0 = now_ms();
-    if ((e = box.ensure((size_t)b.stride * (size_t)x.n_grids * sizeof(int16_t))) != hipSuccess) return e;
+    if ((e = box.ensure_exact((size_t)b.stride * (size_t)x.n_grids * sizeof(int16_t))) != hipSuccess) return e;
     b.g = box.p;
     if ((e = launch_pyr_widen(src, b, x.n_grids, x.stream)) != hipSuccess) return e;
     if ((e = hipStreamSynchronize(x.stream)) != hipSuccess) return e;
@@ -193,20 +171,19 @@ struct PyramidSearch::Impl {
   hipError_t ensure_lists(int D) {
     hipError_t e;
     for (int d = 0; d <= D; ++d) {
-      if ((e = nodes[d].ensure((size_t)capd[d] * sizeof(uint64_t))) != hipSuccess) return e;
-      if ((e = vals[d].ensure((size_t)capd[d] * sizeof(double))) != hipSuccess) return e;
+      if ((e = nodes[d].ensure_exact((size_t)capd[d] * sizeof(uint64_t))) != hipSuccess) return e;
+      if ((e = vals[d].ensure_exact((size_t)capd[d] * sizeof(double))) != hipSuccess) return e;
     }
     const int64_t np = ((int64_t)1 << (2 * D)) * kRoots;
-    if ((e = partials.ensure((size_t)pyr_blocks(INT64_MAX / 2) * sizeof(PyrPartial))) != hipSuccess) return e;
-    if ((e = state.ensure(sizeof(BestPartial) + (kPyrMaxDepth + 1 + kCountSlots) * sizeof(unsigned long long))) !=
+    if ((e = partials.ensure_exact((size_t)pyr_blocks(INT64_MAX / 2) * sizeof(PyrPartial))) != hipSuccess) return e;
+    if ((e = state.ensure_exact(sizeof(BestPartial) + (kPyrMaxDepth + 1 + kCountSlots) * sizeof(unsigned long long))) !=
         hipSuccess)
       return e;
-    if ((e = probe_slot.ensure(kRoots * sizeof(uint64_t))) != hipSuccess) return e;
-    if ((e = probe_nodes.ensure((size_t)np * sizeof(uint64_t))) != hipSuccess) return e;
-    if ((e = probe_vals.ensure((size_t)np * sizeof(double))) != hipSuccess) return e;
-    if (!h_counts && (e = hipHostMalloc((void**)&h_counts,
-                                        (2 + kPyrMaxDepth + 1) * sizeof(unsigned long long) + sizeof(BestPartial),
-                                        hipHostMallocDefault)) != hipSuccess)
+    if ((e = probe_slot.ensure_exact(kRoots * sizeof(uint64_t))) != hipSuccess) return e;
+    if ((e = probe_nodes.ensure_exact((size_t)np * sizeof(uint64_t))) != hipSuccess) return e;
+    if ((e = probe_vals.ensure_exact((size_t)np * sizeof(double))) != hipSuccess) return e;
+    if ((e = h_words.ensure_exact((2 + kPyrMaxDepth + 1) * sizeof(unsigned long long) + sizeof(BestPartial))) !=
+        hipSuccess)
       return e;
     return hipSuccess;
   }
@@ -219,11 +196,10 @@ struct PyramidSearch::Impl {
     const bool timed = in.timed && n_ev_bound < kBoundEvents;
     hipError_t e;
     if (timed) {
-      if (ev_bound.size() < (size_t)2 * kBoundEvents) ev_bound.resize((size_t)2 * kBoundEvents, nullptr);
+      if (ev_bound.size() < (size_t)2 * kBoundEvents) ev_bound.resize((size_t)2 * kBoundEvents);
       ev_bound_depth.resize(kBoundEvents);
       for (int k = 0; k < 2; ++k)
-        if (!ev_bound[2 * n_ev_bound + k] && (e = hipEventCreate(&ev_bound[2 * n_ev_bound + k])) != hipSuccess)
-          return e;
+        if ((e = ev_bound[2 * n_ev_bound + k].create(hipEventDefault)) != hipSuccess) return e;
       if ((e = hipEventRecord(ev_bound[2 * n_ev_bound], in.stream)) != hipSuccess) return e;
     }
     if ((e = launch_pyr_bound(in.L, lev[d], d, in.scans, in.angles, in.pts, in.n_used, in.step, list, n, n_dev, upper,
@@ -280,9 +256,9 @@ struct PyramidSearch::Impl {
   // counts[d - 1] and counts[d] to the host
   hipError_t read_counts(int d) {
     hipError_t e;
-    if ((e = hipMemcpyAsync(h_counts, count_dev(d - 1), sizeof(unsigned long long), hipMemcpyDeviceToHost,
+    if ((e = hipMemcpyAsync(h_counts(), count_dev(d - 1), sizeof(unsigned long long), hipMemcpyDeviceToHost,
                             in.stream)) != hipSuccess ||
-        (e = hipMemcpyAsync(h_counts + 1, count_dev(d), sizeof(unsigned long long), hipMemcpyDeviceToHost,
+        (e = hipMemcpyAsync(h_counts() + 1, count_dev(d), sizeof(unsigned long long), hipMemcpyDeviceToHost,
                             in.stream)) != hipSuccess)
       return e;
     st->syncs += 1;
@@ -315,8 +291,8 @@ struct PyramidSearch::Impl {
     // optimistic: expand everything, then look at the count
     if ((e = expand(d, 0, n, nd, upper)) != hipSuccess) return e;
     if ((e = read_counts(d)) != hipSuccess) return e;
-    const int64_t m = (int64_t)h_counts[0];
-    if (n < 0) n = (int64_t)h_counts[1];
+    const int64_t m = (int64_t)h_counts()[0];
+    if (n < 0) n = (int64_t)h_counts()[1];
     if (m <= capd[d - 1]) return m > 0 ? level_pass(d - 1, m, m, false) : hipSuccess;
     // overflow (children dropped): slices of capacity / 4 parents, each descended
     const int64_t slice = std::max<int64_t>(1, capd[d - 1] / 4);
@@ -384,11 +360,11 @@ hipError_t PyramidSearch::run(const PyrInputs& x, BestPartial* best, PyrStats* s
   if (use_box && (e = I.build_box(x, D, (int32_t)nj, npc)) == hipSuccess) {
     // the split waves' partial sums: only launches of few (window, angle)s split
     const size_t slab_ints = box_blocks < 4096 ? (size_t)n_top * kPyrTopMaxSplit : 0;  // launch_pyr_topbox's rule
-    if ((e = I.top_sums.ensure((size_t)n_top * sizeof(int32_t))) != hipSuccess ||
-        (e = I.top_thr.ensure(2 * sizeof(int64_t))) != hipSuccess ||
-        (slab_ints && (e = I.top_slab.ensure(slab_ints * sizeof(int32_t))) != hipSuccess))
+    if ((e = I.top_sums.ensure_exact((size_t)n_top * sizeof(int32_t))) != hipSuccess ||
+        (e = I.top_thr.ensure_exact(2 * sizeof(int64_t))) != hipSuccess ||
+        (slab_ints && (e = I.top_slab.ensure_exact(slab_ints * sizeof(int32_t))) != hipSuccess))
       return fail(e, "pyramid top level");
-    if ((e = I.partials.ensure((size_t)std::max<int64_t>(box_blocks, pyr_blocks(INT64_MAX / 2)) *
+    if ((e = I.partials.ensure_exact((size_t)std::max<int64_t>(box_blocks, pyr_blocks(INT64_MAX / 2)) *
                                sizeof(PyrPartial))) != hipSuccess)
       return fail(e, "pyramid partials");
     if (x.timed && (e = I.mark_top(0, x.stream)) != hipSuccess) return fail(e, "hipEventRecord");
@@ -413,10 +389,10 @@ hipError_t PyramidSearch::run(const PyrInputs& x, BestPartial* best, PyrStats* s
     return fail(e, "pyramid box level");
   } else if (D > 0 && top_blocks > 0 && n_top <= ((int64_t)1 << 28)) {
     // the whole top level in one launch (column layout), then descend
-    if ((e = I.nodes[D].ensure((size_t)n_top * sizeof(uint64_t))) != hipSuccess ||
-        (e = I.vals[D].ensure((size_t)n_top * sizeof(double))) != hipSuccess)
+    if ((e = I.nodes[D].ensure_exact((size_t)n_top * sizeof(uint64_t))) != hipSuccess ||
+        (e = I.vals[D].ensure_exact((size_t)n_top * sizeof(double))) != hipSuccess)
       return fail(e, "pyramid top level");
-    if ((e = I.partials.ensure((size_t)std::max<int64_t>(top_blocks, pyr_blocks(INT64_MAX / 2)) *
+    if ((e = I.partials.ensure_exact((size_t)std::max<int64_t>(top_blocks, pyr_blocks(INT64_MAX / 2)) *
                                sizeof(PyrPartial))) != hipSuccess)
       return fail(e, "pyramid partials");
     if ((e = launch_pyr_top_bound(x.L, I.lev[D], D, (int32_t)nj, x.scans, x.angles, x.pts, x.n_used, x.step,
