@@ -1059,6 +1059,7 @@ int csm_load_scans_async(csm_ctx* c, int32_t n_scans, const double* pts, const i
   for (auto& o : S.off) o -= offsets[0];
   S.n = n_scans;
   S.from_ranges = false;
+  S.deskewed = false;
   c->staged_count++;
   return CSM_OK;
 }
@@ -1095,6 +1096,8 @@ int take_staged(csm_ctx* c) {
   csm_ctx::Staged& S = c->staged[c->staged_head];
   hipError_t e;
   if ((e = hipEventSynchronize(S.ready)) != hipSuccess) return c->hip_fail(e, "hipEventSynchronize(stage)");
+  if (S.from_ranges && S.deskewed)
+    if (const int rst = repair_deskewed(c, S)) return rst;
   std::swap(c->pts, S.pts);
   if (S.from_ranges) {  // the device's prefix counts, copied down before `ready`
     const int64_t* oh = (const int64_t*)S.off_h.p;

@@ -555,6 +555,22 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState {
     csmh::DevBuf ranges, counts, off_dev;
     csmh::HostBuf off_h;
     bool from_ranges = false;
+    // a ranges batch queued for de-skew (csm_load_ranges_deskewed*,
+    // csm_deskew.cpp): the raw ranges as uploaded (`ranges` then holds the
+    // de-skewed ones), the per-scan and per-segment tables (pinned, then on the
+    // device), one flag per scan and their number (copied down before `ready`)
+    // and the pinned rows a repair or a host-side batch uploads. What
+    // take_staged needs to de-skew flagged scans on the host: the caller's
+    // ranges (unchanged until the batch is taken) and a copy of its plan.
+    csmh::DevBuf raw, plan_dev, flags_dev;
+    csmh::HostBuf plan_h, flags_h, rows_h;
+    bool deskewed = false;
+    csm_laser laser{};
+    double factor = 0.0, threshold = 0.0;
+    const float* src_ranges = nullptr;
+    std::vector<int64_t> seg_off;
+    std::vector<int32_t> seg_close;
+    std::vector<double> seg_poses;
   };
   Staged staged[2];
   int staged_head = 0, staged_count = 0;
@@ -566,6 +582,14 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState {
   bool laser_tab_ready = false;
   int32_t laser_tab_beams = 0;
   uint32_t laser_tab_amin = 0, laser_tab_ainc = 0;
+  // ... and the (cos, sin) of the float-arithmetic beam angles the de-skew
+  // reads (laser_data_processor.cpp:58), on the device and on the host, keyed
+  // and made ready the same way (csm_deskew.cpp)
+  csmh::DevBuf deskew_tab;
+  std::vector<double> deskew_tab_host;
+  bool deskew_tab_ready = false;
+  int32_t deskew_tab_beams = 0;
+  uint32_t deskew_tab_amin = 0, deskew_tab_ainc = 0;
 
   // scans made resident by csm_load_scans (offsets relative to pts)
   int32_t loaded_n = -1;
@@ -631,6 +655,12 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState {
   }
   std::vector<csmh::PendingRun> deferred;  // signalled launches whose timings are read later (flush_deferred)
   std::vector<csm_kernel_stat> stats;
+  // a counter among the stats: `launches` grows by n
+  void account_count(const char* name, int64_t n) {
+    account(name, 0.0f, 0.0, 0.0);
+    for (auto& s : stats)
+      if (std::strncmp(s.name, name, sizeof(s.name)) == 0) s.launches += n - 1;
+  }
   void account(const char* name, float ms, double bytes, double scorings) {
     for (auto& s : stats)
       if (std::strncmp(s.name, name, sizeof(s.name)) == 0) {
@@ -773,6 +803,11 @@ int pipe_drain(csm_ctx* c);
 void pipe_free(csm_ctx* c);
 int open_stage_slot(csm_ctx* c, csm_ctx::Staged** out);
 int take_staged(csm_ctx* c);
+// csm_ranges.cpp: a ranges batch's slot buffers, and the ingest of S.ranges up to S.ready
+int ranges_slot_prepare(csm_ctx* c, csm_ctx::Staged& S, const csm_laser& L, int32_t n_scans);
+int ranges_ingest(csm_ctx* c, csm_ctx::Staged& S, const csm_laser& L, double threshold, int32_t n_scans, double factor);
+// csm_deskew.cpp: the scans a de-skewed batch's kernel flagged, de-skewed on the host (take_staged, after S.ready)
+int repair_deskewed(csm_ctx* c, csm_ctx::Staged& S);
 int drop_staged(csm_ctx* c);
 int matchers_loaded_locked(csm_ctx* c, const csm_param levels[3], int32_t use_fine, double* poses, double* covs,
                            double* scores);

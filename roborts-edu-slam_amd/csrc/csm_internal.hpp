@@ -337,6 +337,33 @@ hipError_t launch_ranges_offsets(const int32_t* counts, int32_t n_scans, int64_t
 hipError_t launch_ranges_points(const float* ranges, int32_t n_scans, int32_t n_beams, double range_min,
                                 double threshold, double factor, const double* cos_sin, const int64_t* offsets,
                                 double* pts, hipStream_t stream);
+// Motion de-skew on the device (csm_deskew.hip; LaserDataProcessor::Process,
+// laser_data_processor.cpp:43-120). What the host precomputes per segment
+// (BeamsUpdate :247-265) and per scan (the base transform, :289). 64 bytes each.
+struct DeskewSeg {
+  double x0, det_x, y0, det_y, ya, det_yaw;
+  int32_t first, cnt;   // beams first ... first + cnt - 1 (the last one closes the segment)
+  int32_t host_bin;     // an interior closing beam is the host's: its bin (-1: it writes nothing); -2: the device's
+  float host_range;     // ... and its float32 range
+};
+struct DeskewScan {
+  double r00, r01, r10, r11, tx, ty;  // Transform2d(base, 0)
+  int64_t seg_off;                    // the scan's first DeskewSeg
+  int32_t n_seg, pad;                 // 0: the scan passes through
+};
+static_assert(sizeof(DeskewSeg) == 64 && sizeof(DeskewScan) == 64, "de-skew tables are uploaded as laid out");
+constexpr int32_t kDeskewMaxBeams = 8000;  // n_beams 8-byte LDS slots in one workgroup's 64 KiB
+// raw -> out (n_scans * n_beams float32 each), one workgroup per scan;
+// beam_cs: n_beams (cos, sin) of the float-arithmetic beam angles; trig_tab:
+// libm's sincos table; flags: n_scans + 1 int32 zeroed by the caller (flags[s]
+// = 1 for a scan with a beam the guard could not decide, flags[n_scans] their
+// number).
+hipError_t launch_deskew(const float* raw, int32_t n_scans, int32_t n_beams, float angle_min, float angle_increment,
+                         const DeskewScan* scans, const DeskewSeg* segs, const double* beam_cs,
+                         const double* trig_tab, float* out, int32_t* flags, hipStream_t stream);
+// out[i] = atan2(y[i], x[i]) / sqrt(x[i]) as the de-skew kernel computes them
+hipError_t launch_atan2(const double* y, const double* x, int64_t n, double* out, hipStream_t stream);
+hipError_t launch_sqrt(const double* x, int64_t n, double* out, hipStream_t stream);
 hipError_t launch_build_palette(const int32_t* gridi, int64_t n, int32_t* scratch, int32_t* vals, int32_t* state,
                                 uint8_t* idx, hipStream_t stream);
 // v11 pair box kernel: palettes of at most kPairMaxPal values, read from

@@ -73,21 +73,12 @@ struct IngestTimer {
   }
 };
 
-// csm_load_ranges_async once locked: the batch into the next free slot, all of
-// it enqueued on stage_stream before S.ready. Nothing but this call's work
-// writes the slot's buffers (the submit path parks a pending batch's points in
-// a taken slot until the call that queues into it next).
-int queue_ranges(csm_ctx* c, const csm_laser* laser, int32_t n_scans, const float* ranges, double factor) {
-  if (!laser) return c->fail(CSM_ERR_INVALID_ARG, "null laser");
-  const csm_laser L = *laser;
-  double threshold = 0.0;
-  if (!csm::laser_threshold(L, &threshold))
-    return c->fail(CSM_ERR_INVALID_ARG, "bad laser (n_beams <= 0, range_min >= range_max or a field not finite)");
-  if (n_scans < 0 || (n_scans > 0 && !ranges)) return c->fail(CSM_ERR_INVALID_ARG, "bad ranges");
+}  // namespace
+
+// A ranges batch's slot buffers (the ranges as float32, the counts, offsets
+// and the most points the batch can keep) and the laser's table.
+int ranges_slot_prepare(csm_ctx* c, csm_ctx::Staged& S, const csm_laser& L, int32_t n_scans) {
   int st;
-  csm_ctx::Staged* slot = nullptr;
-  if ((st = open_stage_slot(c, &slot)) != CSM_OK) return st;
-  csm_ctx::Staged& S = *slot;
   hipError_t e;
   if ((st = ensure_laser_table(c, L)) != CSM_OK) return st;
   const int64_t n_ranges = (int64_t)n_scans * L.n_beams;  // the most points the batch can keep
@@ -100,6 +91,17 @@ int queue_ranges(csm_ctx* c, const csm_laser* laser, int32_t n_scans, const floa
       (e = S.maxabs_dev.ensure(sizeof(unsigned long long))) != hipSuccess)
     return c->hip_fail(e, "hipMalloc(stage)");
   if ((e = S.off_h.ensure(off_bytes)) != hipSuccess) return c->hip_fail(e, "hipHostMalloc(stage offsets)");
+  return CSM_OK;
+}
+
+// The ingest of S.ranges (already enqueued on stage_stream): the points, their
+// offsets and max |x| + |y|, copied down before S.ready.
+int ranges_ingest(csm_ctx* c, csm_ctx::Staged& S, const csm_laser& L, double threshold, int32_t n_scans,
+                  double factor) {
+  hipError_t e;
+  const int64_t n_ranges = (int64_t)n_scans * L.n_beams;
+  const size_t range_bytes = (size_t)n_ranges * sizeof(float);
+  const size_t off_bytes = ((size_t)n_scans + 1) * sizeof(int64_t);
   hipStream_t s = c->stage_stream;
   const double lo = (double)L.range_min;
   IngestTimer tm(c->profiling && !c->profile_first_level);
@@ -108,9 +110,8 @@ int queue_ranges(csm_ctx* c, const csm_laser* laser, int32_t n_scans, const floa
   // kept count stays on the device, so points_maxabs_kernel runs over the
   // upper bound, and a zero point leaves its maximum as it is.
   if ((e = hipMemsetAsync(S.maxabs_dev.p, 0, sizeof(unsigned long long), s)) != hipSuccess ||
-      (n_ranges > 0 && (e = hipMemsetAsync(S.pts.p, 0, (size_t)n_ranges * 2 * sizeof(double), s)) != hipSuccess) ||
-      (n_ranges > 0 && (e = hipMemcpyAsync(S.ranges.p, ranges, range_bytes, hipMemcpyHostToDevice, s)) != hipSuccess))
-    return c->hip_fail(e, "csm_load_ranges_async(upload)");
+      (n_ranges > 0 && (e = hipMemsetAsync(S.pts.p, 0, (size_t)n_ranges * 2 * sizeof(double), s)) != hipSuccess))
+    return c->hip_fail(e, "csm_load_ranges_async(memset)");
   tm.mark(0, s);
   if ((e = csm::launch_ranges_count((const float*)S.ranges.p, n_scans, L.n_beams, lo, threshold,
                                     (int32_t*)S.counts.p, s)) != hipSuccess)
@@ -133,13 +134,38 @@ int queue_ranges(csm_ctx* c, const csm_laser* laser, int32_t n_scans, const floa
     return c->hip_fail(e, "csm_load_ranges_async");
   if (tm.on && hipEventSynchronize(S.ready) == hipSuccess)  // the kept count is down: what the points pass wrote
     tm.report(c, (double)range_bytes, (double)((const int64_t*)S.off_h.p)[n_scans] * 2 * sizeof(double));
+  return CSM_OK;
+}
+
+// csm_load_ranges_async once locked: the batch into the next free slot, all of
+// it enqueued on stage_stream before S.ready. Nothing but this call's work
+// writes the slot's buffers (the submit path parks a pending batch's points in
+// a taken slot until the call that queues into it next).
+int queue_ranges(csm_ctx* c, const csm_laser* laser, int32_t n_scans, const float* ranges, double factor) {
+  if (!laser) return c->fail(CSM_ERR_INVALID_ARG, "null laser");
+  const csm_laser L = *laser;
+  double threshold = 0.0;
+  if (!csm::laser_threshold(L, &threshold))
+    return c->fail(CSM_ERR_INVALID_ARG, "bad laser (n_beams <= 0, range_min >= range_max or a field not finite)");
+  if (n_scans < 0 || (n_scans > 0 && !ranges)) return c->fail(CSM_ERR_INVALID_ARG, "bad ranges");
+  int st;
+  csm_ctx::Staged* slot = nullptr;
+  if ((st = open_stage_slot(c, &slot)) != CSM_OK) return st;
+  csm_ctx::Staged& S = *slot;
+  hipError_t e;
+  if ((st = ranges_slot_prepare(c, S, L, n_scans)) != CSM_OK) return st;
+  const size_t range_bytes = (size_t)n_scans * L.n_beams * sizeof(float);
+  if (range_bytes > 0 && (e = hipMemcpyAsync(S.ranges.p, ranges, range_bytes, hipMemcpyHostToDevice,
+                                             c->stage_stream)) != hipSuccess)
+    return c->hip_fail(e, "csm_load_ranges_async(upload)");
+  if ((st = ranges_ingest(c, S, L, threshold, n_scans, factor)) != CSM_OK) return st;
   S.n = n_scans;
   S.from_ranges = true;
+  S.deskewed = false;
   c->staged_count++;
   return CSM_OK;
 }
 
-}  // namespace
 }  // namespace csmh
 
 using namespace csmh;

@@ -382,6 +382,53 @@ class Context:
                                                float(factor)))
         q.append((r.shape[0], r))
 
+    def load_ranges_deskewed(self, laser, ranges, factor: float, seg_offsets, seg_close, poses):
+        """csm_load_ranges_deskewed: load_ranges of the scans de-skewed on the
+        device (LaserDataProcessor::Process); the plan as deskew_ranges takes it."""
+        L = _as_laser(laser)
+        r = _as_ranges(ranges, L)
+        off, close, ps = _as_deskew_plan(r.shape[0], seg_offsets, seg_close, poses)
+        self._loaded = (r.shape[0], r)
+        queued = self.__dict__.get("_queued")  # the library drops queued batches too (after the call)
+        try:
+            self._check(_lib.csm_load_ranges_deskewed(self._h, C.byref(L), r.shape[0], r.ctypes.data_as(_abi._f32p),
+                                                      float(factor), _i64ptr(off), close.ctypes.data_as(_abi._i32p),
+                                                      _dptr(ps)))
+        finally:
+            if queued is not None and self.__dict__.get("_queued") is queued:
+                self.__dict__.pop("_queued", None)
+
+    def load_ranges_deskewed_async(self, laser, ranges, factor: float, seg_offsets, seg_close, poses):
+        """csm_load_ranges_deskewed_async: load_ranges_async of the de-skewed
+        scans. `ranges` should be pinned and must not change until the batch
+        is taken (a flagged scan is de-skewed from them then); the plan
+        arrays are read during the call only."""
+        L = _as_laser(laser)
+        r = _as_ranges(ranges, L)
+        off, close, ps = _as_deskew_plan(r.shape[0], seg_offsets, seg_close, poses)
+        q = self.__dict__.setdefault("_queued", [])
+        self._check(_lib.csm_load_ranges_deskewed_async(self._h, C.byref(L), r.shape[0],
+                                                        r.ctypes.data_as(_abi._f32p), float(factor), _i64ptr(off),
+                                                        close.ctypes.data_as(_abi._i32p), _dptr(ps)))
+        q.append((r.shape[0], r))
+
+    def atan2_device(self, y, x):
+        """csm_atan2_device: the device library's atan2(y, x), as the de-skew kernel calls it."""
+        a = np.ascontiguousarray(y, dtype=np.float64).ravel()
+        b = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        if a.size != b.size:
+            raise ValueError("y and x differ in size")
+        out = np.empty_like(a)
+        self._check(_lib.csm_atan2_device(self._h, _dptr(a), _dptr(b), a.size, _dptr(out)))
+        return out
+
+    def sqrt_device(self, x):
+        """csm_sqrt_device: the device's sqrt, as the de-skew kernel calls it."""
+        a = np.ascontiguousarray(x, dtype=np.float64).ravel()
+        out = np.empty_like(a)
+        self._check(_lib.csm_sqrt_device(self._h, _dptr(a), a.size, _dptr(out)))
+        return out
+
     def loaded_scans(self):
         """csm_loaded_scans: the currently loaded set (not a queued one) copied
         back from the device -> (points [N, 2], offsets [n_scans + 1])."""
@@ -645,6 +692,54 @@ def ranges_to_points(laser, ranges, factor: float):
     return pts, off
 
 
+def _as_deskew_plan(n_scans: int, seg_offsets, seg_close, poses):
+    off = np.ascontiguousarray(seg_offsets, dtype=np.int64).ravel()
+    close = np.ascontiguousarray(seg_close, dtype=np.int32).ravel()
+    ps = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 3)
+    if off.size != n_scans + 1:
+        raise ValueError(f"{off.size} segment offsets for {n_scans} scans")
+    n_seg = int(off[-1])
+    if off[0] != 0 or close.size != n_seg or ps.shape[0] != n_seg + n_scans:
+        raise ValueError("the plan needs seg_offsets[-1] closes and one pose more per scan")
+    # (never a null pointer for an empty array: the library tells them apart)
+    if close.size == 0:
+        close = np.zeros(1, dtype=np.int32)
+    if ps.size == 0:
+        ps = np.zeros((1, 3))
+    return off, close, ps
+
+
+def deskew_plan(n_beams: int, start_sec: float, end_sec: float, odom_interpolation_time: float):
+    """csm_deskew_plan (host, no GPU needed): DataCorrect's segmentation
+    -> (seg_close int32 [K], lookup_sec float64 [K]); K = 0 when start_sec >=
+    end_sec (the scan passes through)."""
+    cap = max(int(n_beams), 1)
+    close = np.zeros(cap, dtype=np.int32)
+    sec = np.zeros(cap, dtype=np.float64)
+    n = C.c_int32(0)
+    st = _lib.csm_deskew_plan(int(n_beams), float(start_sec), float(end_sec), float(odom_interpolation_time),
+                              close.ctypes.data_as(_abi._i32p), _dptr(sec), cap, C.byref(n))
+    if st != _abi.CSM_OK:
+        raise CsmError(st, "csm_deskew_plan: bad arguments")
+    return close[:n.value].copy(), sec[:n.value].copy()
+
+
+def deskew_ranges(laser, ranges, seg_offsets, seg_close, poses) -> np.ndarray:
+    """csm_deskew_ranges (host, no GPU needed): LaserDataProcessor::Process
+    over float32 ranges [n_scans, n_beams] -> the de-skewed ranges. Scan s has
+    seg_offsets[s + 1] - seg_offsets[s] closing beams in seg_close and one pose
+    (x, y, tf yaw) more, from pose seg_offsets[s] + s."""
+    L = _as_laser(laser)
+    r = _as_ranges(ranges, L)
+    off, close, ps = _as_deskew_plan(r.shape[0], seg_offsets, seg_close, poses)
+    out = np.empty_like(r)
+    st = _lib.csm_deskew_ranges(C.byref(L), r.shape[0], r.ctypes.data_as(_abi._f32p), _i64ptr(off),
+                                close.ctypes.data_as(_abi._i32p), _dptr(ps), out.ctypes.data_as(_abi._f32p))
+    if st != _abi.CSM_OK:
+        raise CsmError(st, "csm_deskew_ranges: bad laser, plan or poses")
+    return out
+
+
 def build_digest() -> str:
     """The source digest the loaded library was compiled from (csm_build_digest;
     tools/source_digest.py computes the tree's)."""
@@ -749,5 +844,5 @@ __all__ = [
     "ScanMatchers", "CorrelationScanMatchParam", "SIM_YAML_LEVELS", "PARAM_CONFIG_LEVELS",
     "IN_CLASS_LEVELS", "FAST_PARAM", "BasedOptimizeScanMatch", "OptimizeScanMatchParam", "SIM_YAML_OPTIMIZE",
     "PARAM_CONFIG_OPTIMIZE", "CONFIG1_PARAM", "headline_levels", "window_dims",
-    "cell_points", "ranges_to_points", "laser_range_threshold", "COARSE", "FINE", "SUPER", "FAST", "kMapUnknownCellProb",
+    "cell_points", "ranges_to_points", "laser_range_threshold", "deskew_plan", "deskew_ranges", "COARSE", "FINE", "SUPER", "FAST", "kMapUnknownCellProb",
 ]

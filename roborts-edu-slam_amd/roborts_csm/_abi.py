@@ -31,6 +31,8 @@ EXPORTED = (
     "csm_host_alloc", "csm_host_free",
     "csm_laser_range_threshold", "csm_ranges_to_points", "csm_load_ranges", "csm_load_ranges_async",
     "csm_loaded_scans",
+    "csm_deskew_plan", "csm_deskew_ranges", "csm_load_ranges_deskewed", "csm_load_ranges_deskewed_async",
+    "csm_atan2_device", "csm_sqrt_device",
     "csm_set_profiling", "csm_kernel_stats", "csm_sort_order", "csm_phase_buckets",
     "csm_set_grid_stack", "csm_best_windows", "csm_optimize_scan_match", "csm_optimize_scan_match_batch",
     "csm_optimize_update_cost", "csm_load_scans_grids", "csm_scan_matchers_batch_grids",
@@ -253,6 +255,14 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "csm_load_ranges": (C.c_int, [_ctx, C.POINTER(CsmLaser), C.c_int32, _f32p, C.c_double]),
         "csm_load_ranges_async": (C.c_int, [_ctx, C.POINTER(CsmLaser), C.c_int32, _f32p, C.c_double]),
         "csm_loaded_scans": (C.c_int, [_ctx, _i32p, _i64p, C.c_int64, _dp, C.c_int64]),
+        "csm_deskew_plan": (C.c_int, [C.c_int32, C.c_double, C.c_double, C.c_double, _i32p, _dp, C.c_int32, _i32p]),
+        "csm_deskew_ranges": (C.c_int, [C.POINTER(CsmLaser), C.c_int32, _f32p, _i64p, _i32p, _dp, _f32p]),
+        "csm_load_ranges_deskewed": (C.c_int, [_ctx, C.POINTER(CsmLaser), C.c_int32, _f32p, C.c_double, _i64p, _i32p,
+                                               _dp]),
+        "csm_load_ranges_deskewed_async": (C.c_int, [_ctx, C.POINTER(CsmLaser), C.c_int32, _f32p, C.c_double, _i64p,
+                                                     _i32p, _dp]),
+        "csm_atan2_device": (C.c_int, [_ctx, _dp, _dp, C.c_int64, _dp]),
+        "csm_sqrt_device": (C.c_int, [_ctx, _dp, C.c_int64, _dp]),
         "csm_scan_matchers_loaded": (C.c_int, [_ctx, C.POINTER(CsmParam), C.c_int32, _dp, _dp, _dp]),
         "csm_scan_matchers_submit": (C.c_int, [_ctx, C.POINTER(CsmParam), C.c_int32, _dp, _dp, _dp]),
         "csm_scan_matchers_wait": (C.c_int, [C.c_void_p]),
