@@ -564,6 +564,26 @@ int csm_search_windows(csm_ctx* ctx, const double* points_xy, int32_t n_points,
                        const double* centers_map, const csm_search_options* options,
                        csm_best* best, int32_t* best_window, csm_search_stats* stats);
 
+/* Test hook: the search's top-level bounds, read out of the kernels that
+ * compute them. Windows as csm_search_windows; the pooled levels are built or
+ * reused as that call does, then the top level at `depth` (1..10) is bounded
+ * once through the path `kernel` names and one value per top node is copied
+ * out in list order ((window, angle, K, J), J fastest; nj = ceil(n_space /
+ * 2^depth) nodes per axis, n_out = n_windows * n_angles * nj^2 exactly):
+ *   kernel 0  the beam boxes: sums[i] = the node's integer sum over the beams
+ *             in level units (2^12 fixed-point units); bounds is not touched
+ *   kernel 1  the whole-level gathers, kernel 2 the node-list gathers on the
+ *             full list: bounds[i] = the node's bound as the search compares
+ *             it (the 0.45 penalty floor applied); sums is not touched
+ * No probe, no expansion, no incumbent: a following csm_search_windows on the
+ * context is unaffected. CSM_ERR_UNSUPPORTED when the windows are outside the
+ * pooled search (csm_search_windows would search them exhaustively) or, for
+ * kernel 0, when the search would not run the boxes on this input. */
+int csm_search_bounds(csm_ctx* ctx, const double* points_xy, int32_t n_points,
+                      const csm_param* param, int32_t n_windows, const int32_t* grid_index,
+                      const double* centers_map, int32_t depth, int32_t kernel,
+                      double* bounds, int64_t* sums, int64_t n_out);
+
 #ifdef __cplusplus
 }
 #endif

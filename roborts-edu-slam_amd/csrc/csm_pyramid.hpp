@@ -176,6 +176,16 @@ class PyramidSearch {
   PyramidSearch& operator=(const PyramidSearch&) = delete;
   // The best candidate over all windows (score, window * n_cand + flat).
   hipError_t run(const PyrInputs& in, BestPartial* best, PyrStats* stats, std::string* what);
+  // Test hook (csm_search_bounds): the top level at in.depth (>= 1) bounded
+  // once through one path, nothing else of a search. kernel 0: the beam
+  // boxes (launch_pyr_topbox), the int32 node sums widened into sums;
+  // 1: launch_pyr_top_bound, 2: launch_pyr_top + launch_pyr_bound on the whole
+  // list, their doubles into bounds. n_out values in list order ((window,
+  // angle, K, J), J fastest). *unsupported: the path does not take this input
+  // (run would use another); nothing is written then. The levels are built
+  // or reused as run does; the buffers are the hook's own.
+  hipError_t top_bounds(const PyrInputs& in, int kernel, double* bounds, int64_t* sums, int64_t n_out,
+                        bool* unsupported, std::string* what);
   // Nodes per level list (0: 4M) and the smallest level that gets an
   // incumbent probe below the top (0: 4096).
   void configure(int64_t node_capacity, int probe_min_nodes);

@@ -168,6 +168,23 @@ struct PyramidSearch::Impl {
     return hipSuccess;
   }
 
+  // The top level may run as beam boxes (whatever top_mode asks): one-cell
+  // steps are given; the box test needs |t| < 2^24 (box_ok), nj <= 32, a
+  // launch of n_scans * n_angles waves.
+  static bool box_eligible(const PyrInputs& x, int64_t nj, int64_t n_top) {
+    const int64_t box_blocks = (int64_t)x.L.n_scans * x.L.n_angles;
+    return x.depth > 0 && x.box_ok && x.one_scan && pyr_topbox_pieces((int32_t)nj) > 0 && box_blocks <= INT32_MAX &&
+           n_top <= ((int64_t)1 << 28) && x.n_used >= 1 && x.n_used <= 4096;
+  }
+  // ints of the split waves' partial sums (launch_pyr_topbox's rule: only
+  // launches of few (window, angle)s split)
+  static size_t box_slab_ints(const PyrInputs& x, int64_t n_top) {
+    return (int64_t)x.L.n_scans * x.L.n_angles < 4096 ? (size_t)n_top * kPyrTopMaxSplit : 0;
+  }
+
+  // csm_search_bounds' own buffers (a search's lists stay as it left them)
+  DevBuf hook_nodes, hook_vals, hook_sums, hook_slab, hook_partials;
+
   hipError_t ensure_lists(int D) {
     hipError_t e;
     for (int d = 0; d <= D; ++d) {
@@ -355,11 +372,10 @@ hipError_t PyramidSearch::run(const PyrInputs& x, BestPartial* best, PyrStats* s
   // needs |t| < 2^24 (box_ok), nj <= 32, a launch of n_scans * n_angles waves
   const int npc = pyr_topbox_pieces((int32_t)nj);
   const int64_t box_blocks = (int64_t)x.L.n_scans * x.L.n_angles;
-  const bool use_box = D > 0 && x.top_mode == 0 && x.box_ok && x.one_scan && npc > 0 && box_blocks <= INT32_MAX &&
-                       n_top <= ((int64_t)1 << 28) && x.n_used >= 1 && x.n_used <= 4096;
+  const bool use_box = x.top_mode == 0 && Impl::box_eligible(x, nj, n_top);
   if (use_box && (e = I.build_box(x, D, (int32_t)nj, npc)) == hipSuccess) {
     // the split waves' partial sums: only launches of few (window, angle)s split
-    const size_t slab_ints = box_blocks < 4096 ? (size_t)n_top * kPyrTopMaxSplit : 0;  // launch_pyr_topbox's rule
+    const size_t slab_ints = Impl::box_slab_ints(x, n_top);
     if ((e = I.top_sums.ensure_exact((size_t)n_top * sizeof(int32_t))) != hipSuccess ||
         (e = I.top_thr.ensure_exact(2 * sizeof(int64_t))) != hipSuccess ||
         (slab_ints && (e = I.top_slab.ensure_exact(slab_ints * sizeof(int32_t))) != hipSuccess))
@@ -433,6 +449,86 @@ hipError_t PyramidSearch::run(const PyrInputs& x, BestPartial* best, PyrStats* s
   I.n_ev_bound = 0;
   I.st->nodes[D] += top_scored;
   return hipSuccess;
+}
+
+hipError_t PyramidSearch::top_bounds(const PyrInputs& x, int kernel, double* bounds, int64_t* sums, int64_t n_out,
+                                     bool* unsupported, std::string* what) {
+  Impl& I = *p_;
+  PyrStats local;
+  I.st = &local;  // build and build_box note their time there
+  hipError_t e;
+  // every return frees the hook's buffers (each hipFree waits for the device:
+  // fine for a test hook), so a context's memory after the call is what a
+  // search left it with
+  auto done = [&](hipError_t err, const char* msg, bool unsup = false) {
+    I.st = nullptr;
+    I.hook_nodes.release();
+    I.hook_vals.release();
+    I.hook_sums.release();
+    I.hook_slab.release();
+    I.hook_partials.release();
+    if (what && msg) *what = msg;
+    if (unsupported) *unsupported = unsup;
+    return err;
+  };
+  const int D = x.depth;
+  if (D < 1 || D > kPyrMaxDepth || kernel < 0 || kernel > 2) return done(hipErrorInvalidValue, "depth or kernel out of range");
+  const int64_t nj = ((int64_t)x.L.n_space + (1 << D) - 1) >> D;
+  const int64_t n_top = (int64_t)x.L.n_scans * x.L.n_angles * nj * nj;
+  if (n_out != n_top) return done(hipErrorInvalidValue, "n_out is not the top level's node count");
+  if (n_top > ((int64_t)1 << 28)) return done(hipSuccess, "top level too large for one launch", true);
+  if ((e = I.build(x)) != hipSuccess) return done(e, "pyramid levels");
+  if (kernel == 0) {
+    if (!Impl::box_eligible(x, nj, n_top)) return done(hipSuccess, "the box path does not take this input", true);
+    const int npc = pyr_topbox_pieces((int32_t)nj);
+    if ((e = I.build_box(x, D, (int32_t)nj, npc)) == hipErrorInvalidValue)
+      return done(hipSuccess, "the box copy does not fit", true);
+    if (e != hipSuccess) return done(e, "pyramid box level");
+    const size_t slab_ints = Impl::box_slab_ints(x, n_top);
+    if ((e = I.hook_sums.ensure_exact((size_t)n_top * sizeof(int32_t))) != hipSuccess ||
+        (slab_ints && (e = I.hook_slab.ensure_exact(slab_ints * sizeof(int32_t))) != hipSuccess) ||
+        (e = I.hook_partials.ensure_exact((size_t)x.L.n_scans * x.L.n_angles * sizeof(PyrPartial))) != hipSuccess)
+      return done(e, "pyramid top level");
+    if ((e = launch_pyr_topbox(x.L, I.boxg, D, (int32_t)nj, x.scans, x.angles, x.pts, x.n_used, x.step,
+                               (int32_t*)I.hook_sums.p, slab_ints ? (int32_t*)I.hook_slab.p : nullptr,
+                               (PyrPartial*)I.hook_partials.p, x.stream)) != hipSuccess)
+      return done(e, "pyr_topbox_kernel");
+    std::vector<int32_t> h((size_t)n_top);
+    if ((e = hipMemcpyAsync(h.data(), I.hook_sums.p, (size_t)n_top * sizeof(int32_t), hipMemcpyDeviceToHost,
+                            x.stream)) != hipSuccess ||
+        (e = hipStreamSynchronize(x.stream)) != hipSuccess)
+      return done(e, "top sums copy");
+    for (int64_t i = 0; i < n_top; ++i) sums[i] = h[(size_t)i];
+    return done(hipSuccess, nullptr);
+  }
+  if ((e = I.hook_nodes.ensure_exact((size_t)n_top * sizeof(uint64_t))) != hipSuccess ||
+      (e = I.hook_vals.ensure_exact((size_t)n_top * sizeof(double))) != hipSuccess)
+    return done(e, "pyramid top level");
+  if (kernel == 1) {
+    int32_t ktiles, kt, col_blocks;
+    const int top_blocks = pyr_top_blocks(x.L, (int32_t)nj, &ktiles, &kt, &col_blocks);
+    if (top_blocks <= 0) return done(hipSuccess, "top level too large for one launch", true);
+    if ((e = I.hook_partials.ensure_exact((size_t)top_blocks * sizeof(PyrPartial))) != hipSuccess)
+      return done(e, "pyramid partials");
+    if ((e = launch_pyr_top_bound(x.L, I.lev[D], D, (int32_t)nj, x.scans, x.angles, x.pts, x.n_used, x.step,
+                                  (uint64_t*)I.hook_nodes.p, (double*)I.hook_vals.p, (PyrPartial*)I.hook_partials.p,
+                                  x.stream)) != hipSuccess)
+      return done(e, "pyr_top_bound_kernel");
+  } else {
+    if ((e = I.hook_partials.ensure_exact((size_t)pyr_bound_blocks(n_top, x.n_used) * sizeof(PyrPartial))) != hipSuccess)
+      return done(e, "pyramid partials");
+    if ((e = launch_pyr_top(x.L, (int32_t)nj, 0, n_top, (uint64_t*)I.hook_nodes.p, x.stream)) != hipSuccess)
+      return done(e, "pyr_top_kernel");
+    if ((e = launch_pyr_bound(x.L, I.lev[D], D, x.scans, x.angles, x.pts, x.n_used, x.step,
+                              (const uint64_t*)I.hook_nodes.p, n_top, nullptr, n_top, (double*)I.hook_vals.p,
+                              (PyrPartial*)I.hook_partials.p, nullptr, x.stream)) != hipSuccess)
+      return done(e, "pyr_bound_kernel");
+  }
+  if ((e = hipMemcpyAsync(bounds, I.hook_vals.p, (size_t)n_top * sizeof(double), hipMemcpyDeviceToHost, x.stream)) !=
+          hipSuccess ||
+      (e = hipStreamSynchronize(x.stream)) != hipSuccess)
+    return done(e, "top bounds copy");
+  return done(hipSuccess, nullptr);
 }
 
 }  // namespace csm

@@ -608,6 +608,28 @@ class Context:
                      build_ms=st.build_ms, syncs=st.syncs, top_box=bool(st.top_box))
         return b, int(w.value), stats
 
+    def search_bounds(self, points_cells, param, grid_index, centers_map, depth: int, kernel: int) -> np.ndarray:
+        """The search's top-level bounds at `depth`, one per node in list order
+        (window, angle, K, J), read out of one kernel (csm_search_bounds, a
+        test hook). kernel 0: the beam boxes' integer node sums (int64, level
+        units); 1: the whole-level gathers' bounds; 2: the node-list gathers'
+        bounds (float64). CsmError(CSM_ERR_UNSUPPORTED) when that path does
+        not take the input."""
+        pts = np.ascontiguousarray(points_cells, dtype=np.float64).reshape(-1, 2)
+        p = _as_param(param)
+        gi = np.ascontiguousarray(grid_index, dtype=np.int32)
+        ctr = np.ascontiguousarray(centers_map, dtype=np.float64).reshape(-1, 3)
+        assert gi.size == ctr.shape[0]
+        na, ns = window_dims(p)
+        nj = (ns + (1 << int(depth)) - 1) >> int(depth)
+        n = gi.size * na * nj * nj
+        out = np.empty(n, dtype=np.int64 if kernel == 0 else np.float64)
+        self._check(_lib.csm_search_bounds(self._h, _dptr(pts), pts.shape[0], C.byref(p), gi.size,
+                                           gi.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(ctr), int(depth),
+                                           int(kernel), _dptr(out) if kernel != 0 else None,
+                                           _i64ptr(out) if kernel == 0 else None, n))
+        return out
+
 
 class _PinnedBlock:
     """One csm_host_alloc allocation, freed when the last array over it dies."""

@@ -24,10 +24,11 @@ def dims(p):
     return na, ns
 
 
-def window_scores(grid: np.ndarray, pts: np.ndarray, p, center, mres: float, outside=np.float32(0.3)):
-    """Penalised scores of every candidate, enumeration order (theta, x, y)."""
+def geometry(n: int, p, center, mres: float):
+    """A window's candidates and beams: (use, step, angles, rows, xs, ys).
+    use: the divisor; beams range(0, n, step); rows[a] = (cos, sin) of
+    angles[a]; xs, ys: the candidates' positions in cells."""
     na, ns = dims(p)
-    n = pts.shape[0]
     use = int(p.use_point_size)
     if n < 2 * use:                                               # :561-566
         use, step = n, 1
@@ -36,15 +37,39 @@ def window_scores(grid: np.ndarray, pts: np.ndarray, p, center, mres: float, out
     half = (p.search_angle_offset * 2) / 2
     start = center[2] - half
     angles = np.array([start + a * p.search_angle_resolution for a in range(na)])
+    rows = [sincos(angles[a]) for a in range(na)]                # :171-172 (GCC: one sincos)
     x0 = center[0] - (p.search_space_size / mres) * 0.5           # :546
     y0 = center[1] - (p.search_space_size / mres) * 0.5
     f = p.search_space_resolution / mres
     xs = x0 + np.arange(ns) * f                                   # :569
     ys = y0 + np.arange(ns) * f                                   # :572
+    return use, step, angles, rows, xs, ys
+
+
+def penalty_factors(p, center, mres: float, angles, xs, ys):
+    """(dp, ap) of every candidate, enumeration order (:587-603, :718-745)."""
+    na, ns = len(angles), len(xs)
+    g = 0.4 if p.correlation_scan_match_type == 0 else 0.2
+    A = np.repeat(angles, ns * ns)
+    X = np.tile(np.repeat(xs, ns), na)
+    Y = np.tile(ys, na * ns)
+    dx, dy = X - center[0], Y - center[1]
+    d2 = (dx * dx + dy * dy) * (mres * mres)
+    dp = np.maximum(1.0 - (g * d2 / (p.search_space_size / 2)), 0.5)
+    da = (A - center[2]) ** 2
+    ap = np.maximum(1.0 - (0.25 * da / 0.349), 0.9)
+    return dp, ap
+
+
+def window_scores(grid: np.ndarray, pts: np.ndarray, p, center, mres: float, outside=np.float32(0.3)):
+    """Penalised scores of every candidate, enumeration order (theta, x, y)."""
+    na, ns = dims(p)
+    n = pts.shape[0]
+    use, step, angles, rows, xs, ys = geometry(n, p, center, mres)
     H, W = grid.shape
     out = np.empty((na, ns, ns))
     for a in range(na):
-        c, s = sincos(angles[a])                                 # :171-172 (GCC: one sincos)
+        c, s = rows[a]
         acc = np.zeros((ns, ns))
         for q in range(0, n, step):                               # :645
             px, py = pts[q, 0], pts[q, 1]
@@ -58,15 +83,7 @@ def window_scores(grid: np.ndarray, pts: np.ndarray, p, center, mres: float, out
         out[a] = acc / use                                        # :659
     sc = out.reshape(-1)
     if p.use_center_penalty:                                      # :587-603, :718-745
-        g = 0.4 if p.correlation_scan_match_type == 0 else 0.2
-        A = np.repeat(angles, ns * ns)
-        X = np.tile(np.repeat(xs, ns), na)
-        Y = np.tile(ys, na * ns)
-        dx, dy = X - center[0], Y - center[1]
-        d2 = (dx * dx + dy * dy) * (mres * mres)
-        dp = np.maximum(1.0 - (g * d2 / (p.search_space_size / 2)), 0.5)
-        da = (A - center[2]) ** 2
-        ap = np.maximum(1.0 - (0.25 * da / 0.349), 0.9)
+        dp, ap = penalty_factors(p, center, mres, angles, xs, ys)
         zero = np.abs(sc) <= 1e-06
         sc = np.where(zero, sc, sc * (dp * ap))
     return sc, angles, xs, ys
