@@ -158,10 +158,7 @@ int queue_deskewed(csm_ctx* c, const csm_laser* laser, int32_t n_scans, const fl
       return c->hip_fail(e, "csm_load_ranges_deskewed(upload)");
     if ((st = ranges_ingest(c, S, L, threshold, n_scans, factor)) != CSM_OK) return st;
     c->account_count("deskew:host_batches", 1);
-    S.n = n_scans;
-    S.from_ranges = true;
-    S.deskewed = false;  // nothing left to repair
-    c->staged_count++;
+    commit_staged(c, S, csm_ctx::StagedKind::kRanges, n_scans);  // nothing left to repair
     return CSM_OK;
   }
 
@@ -206,10 +203,7 @@ int queue_deskewed(csm_ctx* c, const csm_laser* laser, int32_t n_scans, const fl
     S.seg_poses.assign(poses, poses + (n_seg + n_scans) * 3);
   else
     S.seg_poses.clear();
-  S.n = n_scans;
-  S.from_ranges = true;
-  S.deskewed = true;
-  c->staged_count++;
+  commit_staged(c, S, csm_ctx::StagedKind::kDeskewed, n_scans);
   return CSM_OK;
 }
 
@@ -219,7 +213,7 @@ int queue_deskewed(csm_ctx* c, const csm_laser* laser, int32_t n_scans, const fl
 // host restatement, their rows uploaded over the device's, and the ingest run
 // again (its results replace the first run's before anything has read them).
 int repair_deskewed(csm_ctx* c, csm_ctx::Staged& S) {
-  const int32_t n_scans = S.n;
+  const int32_t n_scans = S.batch.n_scans;
   const int32_t* flags = (const int32_t*)S.flags_h.p;
   const int32_t total = n_scans > 0 ? flags[n_scans] : 0;
   c->account_count("deskew:host_scans", total);
@@ -316,11 +310,8 @@ int csm_load_ranges_deskewed(csm_ctx* c, const csm_laser* laser, int32_t n_scans
   if (!c) return CSM_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  if (const int dst = pipe_drain(c)) return dst;  // a submitted batch still reads the context
   int st;
-  c->loaded_n = -1;
-  c->loaded_grid.clear();
-  if ((st = drop_staged(c)) != CSM_OK) return st;
+  if ((st = unload_batch(c)) != CSM_OK) return st;
   // through a staging slot (none is queued now), taken at once
   if ((st = queue_deskewed(c, laser, n_scans, ranges, factor, seg_offsets, seg_close, poses_xyyaw)) != CSM_OK)
     return st;

@@ -5,8 +5,10 @@
 //   csm_api.cpp          context lifetime, profiling, raw window kernels, the search
 //   csm_grid.cpp         resident grids: upload, refresh, stacks, borrowed maps
 //   csm_launch.cpp       window plans and kernel launches (run_windows), joins
-//   csm_driver.cpp       BasedCorrelationScanMatch / ScanMatchers batches, the
-//                        pipelined 3-level driver
+//   csm_level.cpp        one level over a batch: planned, launched, joined, completed
+//   csm_pipeline.cpp     the pipelined 3-level driver, submitted batches in flight
+//   csm_batch.cpp        the resident batch of scans: loaded, queued, taken
+//   csm_driver.cpp       the BasedCorrelationScanMatch / ScanMatchers entry points
 //   csm_host_finish.cpp  the host finish: std::sort, FindBest, covariance,
 //                        the FAST (branch-and-bound) replay
 //   csm_optimize_host.cpp the Gauss-Newton matcher's host loop
@@ -14,9 +16,10 @@
 // Ownership is a property of the types (csm_resources.hpp): every buffer,
 // event and stream of the context frees itself, so csm_destroy only drains
 // and deletes. What one part of a batch needs per launch is LaunchSlot, what a
-// resident grid is GridState; the context is one of each (its bases) and holds
-// the others in alt[] and parked[], exchanged whole by swap_slot / swap_grid:
-// a field added to either struct is swapped, parked and freed with it.
+// resident grid is GridState, what a resident batch of scans is ScanBatch; the
+// context is one of each (its bases) and holds the others in alt[], parked[]
+// and staged[].batch, exchanged whole by swap_slot / swap_grid / swap_batch:
+// a field added to any of the structs is swapped, parked and freed with it.
 //
 // Compiled with g++ -O2 -ffp-contract=off (no -march), like the reference's
 // Release build, so every host double expression rounds as the reference's
@@ -421,11 +424,32 @@ struct GridState {
   uint64_t last_use = 0;     // csm_ctx::grid_clock when it was last selected
 };
 
-static_assert(kMoveOnly<LaunchSlot> && kMoveOnly<GridState>, "slots and grids are exchanged, never copied");
+// A resident batch of scans: the context is one (the batch the next match
+// runs) and holds the queued and parked ones in csm_ctx::Staged::batch;
+// swap_batch exchanges them whole. Exchanged, never assigned across: a pending
+// submitted batch's last launch reads its offsets through PipeJob::offsets,
+// and a vector's data pointer survives swaps (csm_pipeline.cpp).
+struct ScanBatch {
+  DevBuf pts;                      // the points on the device (every part reads them)
+  std::vector<int64_t> scan_off;   // n_scans + 1 offsets relative to pts
+  std::vector<int32_t> scan_grid;  // per scan: the resident grid it is matched on (empty: grid 0)
+  int32_t n_scans = -1;            // -1: no batch loaded
+  double pts_maxabs = 0.0;         // max |x| + |y| of the points (NaN: unbounded)
+  // pts equals csm_ctx::pts_host (upload_points skips an identical upload):
+  // only ever of the context's own batch, so swap_batch clears it on both sides
+  bool pts_cached = false;
+  void unload() {
+    n_scans = -1;
+    scan_grid.clear();
+  }
+};
+
+static_assert(kMoveOnly<LaunchSlot> && kMoveOnly<GridState> && kMoveOnly<ScanBatch>,
+              "slots, grids and batches are exchanged, never copied");
 
 }  // namespace csmh
 
-struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState {
+struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState, csmh::ScanBatch {
   int device = 0;
   // Signalled levels of the 3-level driver: the host completes (and plans the
   // next level of) the windows the fast pass settled while the exact pass
@@ -456,7 +480,6 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState {
     pool->run(n, threads, std::forward<F>(fn));
   }
 
-  csmh::DevBuf pts;         // the resident batch's points (every part reads them)
   csmh::DevBuf best_tiles;  // tiled box mode: one best per (window, tile) between the two reductions
   csmh::HostBuf h_search;   // csm_search_windows: pinned staging of the points and angle table
   bool staging_dirty = false;  // a search failed with copies out of its staging possibly in flight
@@ -505,9 +528,9 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState {
   csmh::Event ev_pack;   // the last copy out of h_pack (cell updates return before it ends)
   bool ev_pack_used = false;
   // the points last uploaded (upload_points skips an identical upload: the
-  // reference's ScanMatchers calls each level with the same range data)
+  // reference's ScanMatchers calls each level with the same range data;
+  // ScanBatch::pts_cached)
   std::vector<double> pts_host;
-  bool pts_cached = false;
   csmh::DevBuf d_updates;  // csm_update_grid_cells entries on the device
 
   // Resident grids of other host maps. csm_set_grid keys a grid on the host
@@ -537,16 +560,18 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState {
   // multi-resolution search.
   uint64_t grid_gen = 0, gen_clock = 0;
   csm::PyramidSearch pyramid;
-  double pts_maxabs = 0.0;   // max |x|+|y| of the resident points (NaN: unbounded)
 
-  // Batches queued by csm_load_scans_async: uploaded on stage_stream (not on
-  // h2d, whose per-launch input copies would queue behind a batch), their
-  // max |x| + |y| found on the device; csm_scan_matchers_loaded swaps the
-  // oldest into `pts` (the old buffer takes the next batch).
+  // Batches queued by csm_load_scans_async / csm_load_ranges*: uploaded on
+  // stage_stream (not on h2d, whose per-launch input copies would queue behind
+  // a batch), their max |x| + |y| found on the device; take_staged swaps the
+  // oldest with the context's batch (the outgoing one parks in the slot until
+  // the next batch is queued into it). `batch` is what is swapped; the rest is
+  // staging only.
+  enum class StagedKind { kPoints, kRanges, kDeskewed };
   struct Staged {
-    csmh::DevBuf pts, maxabs_dev;
-    std::vector<int64_t> off;
-    int32_t n = -1;
+    csmh::ScanBatch batch;
+    StagedKind kind = StagedKind::kPoints;
+    csmh::DevBuf maxabs_dev;
     csmh::Event ready;
     csmh::HostBuf maxabs_h;  // pinned: the 8 bytes of maxabs_dev, copied down before `ready`
     // a batch queued as raw ranges (csm_load_ranges*): the ranges as uploaded,
@@ -554,7 +579,6 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState {
     // memory before `ready` (take_staged reads them where it reads maxabs_h)
     csmh::DevBuf ranges, counts, off_dev;
     csmh::HostBuf off_h;
-    bool from_ranges = false;
     // a ranges batch queued for de-skew (csm_load_ranges_deskewed*,
     // csm_deskew.cpp): the raw ranges as uploaded (`ranges` then holds the
     // de-skewed ones), the per-scan and per-segment tables (pinned, then on the
@@ -564,7 +588,6 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState {
     // ranges (unchanged until the batch is taken) and a copy of its plan.
     csmh::DevBuf raw, plan_dev, flags_dev;
     csmh::HostBuf plan_h, flags_h, rows_h;
-    bool deskewed = false;
     csm_laser laser{};
     double factor = 0.0, threshold = 0.0;
     const float* src_ranges = nullptr;
@@ -574,6 +597,12 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState {
   };
   Staged staged[2];
   int staged_head = 0, staged_count = 0;
+  // Exchange the context's batch with a queued or parked one, whole. Neither
+  // is the one pts_host mirrors afterwards.
+  void swap_batch(csmh::ScanBatch& b) {
+    std::swap(static_cast<csmh::ScanBatch&>(*this), b);
+    pts_cached = b.pts_cached = false;
+  }
   // The laser's per-beam (cos a_i, sin a_i) on the device (csm_ranges.cpp),
   // keyed on (n_beams, angle_min bits, angle_increment bits): uploaded once
   // per key on stage_stream, ready only once the copy was enqueued and the
@@ -590,11 +619,6 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState {
   bool deskew_tab_ready = false;
   int32_t deskew_tab_beams = 0;
   uint32_t deskew_tab_amin = 0, deskew_tab_ainc = 0;
-
-  // scans made resident by csm_load_scans (offsets relative to pts)
-  int32_t loaded_n = -1;
-  std::vector<int64_t> loaded_off;
-  std::vector<int32_t> loaded_grid;  // per loaded scan: the resident grid it is matched on (empty: grid 0)
 
   // per-kernel HIP-event timing (csm_set_profiling / csm_kernel_stats)
   bool profiling = false;
@@ -630,7 +654,7 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState {
   int first_windows_submit = 512;  // (CSM_FIRST_WINDOWS sets both, CSM_FIRST_WINDOWS_SUBMIT this one)
   int first_windows_submit_min_use = 512;
   int span_growth = 4;       // ... and each later span's growth
-  void* pipe = nullptr;  // csm_driver.cpp PipeState: submitted batches (csm_scan_matchers_submit)
+  void* pipe = nullptr;  // csm_pipeline.cpp PipeState: submitted batches (csm_scan_matchers_submit)
   bool split_last_handoff = true;  // the last part's hand-off to the last level in two spans
   int split_handoff_min = 256;     // ... for parts of at least this many windows (CSM_SPLIT_HANDOFF_MIN)
   bool defer_last_handoff = true;  // a submitted batch leaves its last part's last hand-off to the next call (CSM_DEFER_HANDOFF)
@@ -786,7 +810,7 @@ int check_offsets(csm_ctx* c, int32_t n_scans, const int64_t* offsets);
 int match_level_fast(csm_ctx* c, int32_t n_scans, const int64_t* offsets, const csm_param& P,
                      double* poses, double* covs, double* responses, int64_t* argmax_flat);
 
-// csm_driver.cpp
+// csm_level.cpp
 int match_level(csm_ctx* c, int32_t n_scans, const int64_t* offsets, const csm_param& P,
                 double* poses, double* covs, double* responses, int64_t* argmax_flat,
                 const int32_t* scan_grid = nullptr, int skip_lists = 0);
@@ -797,18 +821,26 @@ constexpr double kOptMaxCost = 1.0 * kOptCostPointSize;   // :235
 
 inline bool map_ready(const csm_ctx* c) { return c->has_grid && c->info.update_index >= 0; }
 
-// csm_driver.cpp: a submitted batch still pending is completed (every entry
+// csm_pipeline.cpp: a submitted batch still pending is completed (every entry
 // point but csm_scan_matchers_submit calls it first); the state's release
 int pipe_drain(csm_ctx* c);
 void pipe_free(csm_ctx* c);
+// csm_batch.cpp: no batch loaded, none pending, none queued (what a synchronous load starts from)
+int unload_batch(csm_ctx* c);
+int load_scans_locked(csm_ctx* c, int32_t n_scans, const double* pts, const int64_t* offsets);
+// ... the slot the next queued batch goes into; the end of what a queueing call
+// puts on stage_stream (the slot's max |x| + |y| over n_points of its points,
+// copied down, then S.ready); the queued slot committed; the oldest one taken
 int open_stage_slot(csm_ctx* c, csm_ctx::Staged** out);
+hipError_t stage_maxabs_ready(csm_ctx* c, csm_ctx::Staged& S, int64_t n_points);
+void commit_staged(csm_ctx* c, csm_ctx::Staged& S, csm_ctx::StagedKind kind, int32_t n_scans);
 int take_staged(csm_ctx* c);
 // csm_ranges.cpp: a ranges batch's slot buffers, and the ingest of S.ranges up to S.ready
 int ranges_slot_prepare(csm_ctx* c, csm_ctx::Staged& S, const csm_laser& L, int32_t n_scans);
 int ranges_ingest(csm_ctx* c, csm_ctx::Staged& S, const csm_laser& L, double threshold, int32_t n_scans, double factor);
 // csm_deskew.cpp: the scans a de-skewed batch's kernel flagged, de-skewed on the host (take_staged, after S.ready)
 int repair_deskewed(csm_ctx* c, csm_ctx::Staged& S);
-int drop_staged(csm_ctx* c);
+// csm_driver.cpp
 int matchers_loaded_locked(csm_ctx* c, const csm_param levels[3], int32_t use_fine, double* poses, double* covs,
                            double* scores);
 

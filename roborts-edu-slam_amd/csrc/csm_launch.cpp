@@ -1097,7 +1097,7 @@ bool plan_windows_shared(const csm_param& P, const Dims& D, const Geometry& G, i
 }
 
 int upload_points(csm_ctx* c, const double* pts, int64_t n_total, void* pinned) {
-  c->loaded_n = -1;  // the point buffer is shared with csm_load_scans
+  c->unload();  // the point buffer is shared with csm_load_scans
   const size_t nb = (size_t)std::max<int64_t>(n_total, 0) * 2 * sizeof(double);
   if (c->pts_cached && n_total > 0 && c->pts_host.size() * sizeof(double) == nb &&
       std::memcmp(c->pts_host.data(), pts, nb) == 0)

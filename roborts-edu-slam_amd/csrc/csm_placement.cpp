@@ -2,7 +2,7 @@
 // csm_host_plan). The reference matches scans on one host thread
 // (correlate_scan_matcher.h has no threading), so this has no
 // reference counterpart: it sizes the pool that plans and completes the
-// windows (csm_driver.cpp) for one process per GPU. Each
+// windows (csm_level.cpp) for one process per GPU. Each
 // local rank gets a disjoint slice of the CPUs it may run on near its GPU,
 // and as many threads as its share of the cgroup's CPU quota: eight ranks on
 // one node no longer start 8 x 16 pool threads on a 16-CPU quota.

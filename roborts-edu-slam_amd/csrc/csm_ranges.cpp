@@ -1,6 +1,6 @@
 // csm_ranges.cpp — raw laser ranges in (csm_laser_range_threshold,
 // csm_ranges_to_points on the host; csm_load_ranges, csm_load_ranges_async on
-// the device) and the loaded set out again (csm_loaded_scans).
+// the device).
 //
 // The reference hands its matcher a sensor_msgs/LaserScan: the endpoints are
 // built by SlamNode::BuildRangeDataContainer (roborts_slam_node.cpp:290-311)
@@ -87,7 +87,7 @@ int ranges_slot_prepare(csm_ctx* c, csm_ctx::Staged& S, const csm_laser& L, int3
   const size_t off_bytes = ((size_t)n_scans + 1) * sizeof(int64_t);
   if ((e = S.ranges.ensure(std::max<size_t>(range_bytes, 4))) != hipSuccess ||
       (e = S.counts.ensure(((size_t)n_scans + 1) * sizeof(int32_t))) != hipSuccess ||
-      (e = S.off_dev.ensure(off_bytes)) != hipSuccess || (e = S.pts.ensure(point_bytes)) != hipSuccess ||
+      (e = S.off_dev.ensure(off_bytes)) != hipSuccess || (e = S.batch.pts.ensure(point_bytes)) != hipSuccess ||
       (e = S.maxabs_dev.ensure(sizeof(unsigned long long))) != hipSuccess)
     return c->hip_fail(e, "hipMalloc(stage)");
   if ((e = S.off_h.ensure(off_bytes)) != hipSuccess) return c->hip_fail(e, "hipHostMalloc(stage offsets)");
@@ -109,8 +109,7 @@ int ranges_ingest(csm_ctx* c, csm_ctx::Staged& S, const csm_laser& L, double thr
   // kernel reads its buffers any more. The points buffer is zeroed whole: the
   // kept count stays on the device, so points_maxabs_kernel runs over the
   // upper bound, and a zero point leaves its maximum as it is.
-  if ((e = hipMemsetAsync(S.maxabs_dev.p, 0, sizeof(unsigned long long), s)) != hipSuccess ||
-      (n_ranges > 0 && (e = hipMemsetAsync(S.pts.p, 0, (size_t)n_ranges * 2 * sizeof(double), s)) != hipSuccess))
+  if (n_ranges > 0 && (e = hipMemsetAsync(S.batch.pts.p, 0, (size_t)n_ranges * 2 * sizeof(double), s)) != hipSuccess)
     return c->hip_fail(e, "csm_load_ranges_async(memset)");
   tm.mark(0, s);
   if ((e = csm::launch_ranges_count((const float*)S.ranges.p, n_scans, L.n_beams, lo, threshold,
@@ -121,16 +120,12 @@ int ranges_ingest(csm_ctx* c, csm_ctx::Staged& S, const csm_laser& L, double thr
     return c->hip_fail(e, "ranges_offsets_kernel");
   tm.mark(2, s);
   if ((e = csm::launch_ranges_points((const float*)S.ranges.p, n_scans, L.n_beams, lo, threshold, factor,
-                                     (const double*)c->laser_tab.p, (const int64_t*)S.off_dev.p, (double*)S.pts.p,
+                                     (const double*)c->laser_tab.p, (const int64_t*)S.off_dev.p, (double*)S.batch.pts.p,
                                      s)) != hipSuccess)
     return c->hip_fail(e, "ranges_points_kernel");
   tm.mark(3, s);
-  if ((e = csm::launch_points_maxabs((const double*)S.pts.p, n_ranges, (unsigned long long*)S.maxabs_dev.p, s)) !=
-          hipSuccess ||
-      (e = hipMemcpyAsync(S.maxabs_h.p, S.maxabs_dev.p, sizeof(unsigned long long), hipMemcpyDeviceToHost, s)) !=
-          hipSuccess ||
-      (e = hipMemcpyAsync(S.off_h.p, S.off_dev.p, off_bytes, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-      (e = hipEventRecord(S.ready, s)) != hipSuccess)
+  if ((e = hipMemcpyAsync(S.off_h.p, S.off_dev.p, off_bytes, hipMemcpyDeviceToHost, s)) != hipSuccess ||
+      (e = stage_maxabs_ready(c, S, n_ranges)) != hipSuccess)
     return c->hip_fail(e, "csm_load_ranges_async");
   if (tm.on && hipEventSynchronize(S.ready) == hipSuccess)  // the kept count is down: what the points pass wrote
     tm.report(c, (double)range_bytes, (double)((const int64_t*)S.off_h.p)[n_scans] * 2 * sizeof(double));
@@ -159,10 +154,7 @@ int queue_ranges(csm_ctx* c, const csm_laser* laser, int32_t n_scans, const floa
                                              c->stage_stream)) != hipSuccess)
     return c->hip_fail(e, "csm_load_ranges_async(upload)");
   if ((st = ranges_ingest(c, S, L, threshold, n_scans, factor)) != CSM_OK) return st;
-  S.n = n_scans;
-  S.from_ranges = true;
-  S.deskewed = false;
-  c->staged_count++;
+  commit_staged(c, S, csm_ctx::StagedKind::kRanges, n_scans);
   return CSM_OK;
 }
 
@@ -208,42 +200,11 @@ int csm_load_ranges(csm_ctx* c, const csm_laser* laser, int32_t n_scans, const f
   if (!c) return CSM_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(c->mu);
   DeviceGuard g(c->device);
-  if (const int dst = pipe_drain(c)) return dst;  // a submitted batch still reads the context
   int st;
-  c->loaded_n = -1;
-  c->loaded_grid.clear();
-  if ((st = drop_staged(c)) != CSM_OK) return st;
+  if ((st = unload_batch(c)) != CSM_OK) return st;
   // through a staging slot (none is queued now), taken at once
   if ((st = queue_ranges(c, laser, n_scans, ranges, factor)) != CSM_OK) return st;
   return take_staged(c);
-}
-
-int csm_loaded_scans(csm_ctx* c, int32_t* n_scans, int64_t* point_offsets, int64_t offsets_capacity,
-                     double* points_xy, int64_t capacity_points) {
-  if (!c || !n_scans) return CSM_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  if (const int dst = pipe_drain(c)) return dst;
-  if (c->loaded_n < 0) return c->fail(CSM_ERR_INVALID_ARG, "no scans loaded (csm_load_scans)");
-  const int32_t n = c->loaded_n;
-  *n_scans = n;
-  const int64_t total = n > 0 ? c->loaded_off[(size_t)n] : 0;
-  if (point_offsets) {
-    if (offsets_capacity < (int64_t)n + 1) return c->fail(CSM_ERR_INVALID_ARG, "offsets capacity below n_scans + 1");
-    if (n > 0)
-      std::memcpy(point_offsets, c->loaded_off.data(), ((size_t)n + 1) * sizeof(int64_t));
-    else
-      point_offsets[0] = 0;
-  }
-  if (points_xy) {
-    if (capacity_points < total) return c->fail(CSM_ERR_INVALID_ARG, "points capacity below the loaded point count");
-    hipError_t e;
-    if (total > 0 && ((e = hipMemcpyAsync(points_xy, c->pts.p, (size_t)total * 2 * sizeof(double),
-                                          hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
-                      (e = hipStreamSynchronize(c->stream)) != hipSuccess))
-      return c->hip_fail(e, "hipMemcpy(loaded points)");
-  }
-  return CSM_OK;
 }
 
 }  // extern "C"

@@ -1,7 +1,9 @@
 // resources_check.cpp — ownership of csmh::Buffer (csrc/csm_resources.hpp)
 // over a counting malloc / free policy, without HIP: what ensure and
 // ensure_exact ask for, what a failed allocation leaves, and that moves, swaps
-// and the eviction pattern free every allocation exactly once. Stand-alone
+// and the eviction pattern free every allocation exactly once; and that the
+// resident batch, exchanged whole through the submit sequence, keeps a pending
+// job's offsets where its pointer reads them. Stand-alone
 // (tests/test_resources.py builds and runs it, once more under ASan + UBSan).
 #define CSM_RESOURCES_NO_HIP
 #include "csm_resources.hpp"
@@ -200,6 +202,83 @@ void eviction() {
   CHECK(CountingMem::balanced());
 }
 
+// Stands in for ScanBatch (csm_host.hpp): the points' buffer, the offsets, the
+// per-scan grids, the scan count, the points' bound and the cache flag; and for
+// the context, which is one and exchanges it whole (csm_ctx::swap_batch).
+struct Batch {
+  Buf pts;
+  std::vector<int64_t> off;
+  std::vector<int32_t> grid;
+  int32_t n = -1;
+  double maxabs = 0.0;
+  bool cached = false;
+};
+static_assert(csmh::kMoveOnly<Batch>, "a batch is exchanged, never copied");
+
+struct Ctx : Batch {
+  void swap_batch(Batch& b) {
+    std::swap(static_cast<Batch&>(*this), b);
+    cached = b.cached = false;
+  }
+};
+
+void fill_batch(Batch& b, std::vector<int64_t> off, double maxabs) {  // a load, or a queueing call into a slot
+  CHECK(b.pts.ensure((size_t)off.back() * 16) == 0);
+  b.off.assign(off.begin(), off.end());
+  b.grid.clear();
+  b.n = (int32_t)off.size() - 1;
+  b.maxabs = maxabs;
+}
+
+// csm_scan_matchers_submit over queued batches: batch A loaded and submitted
+// (its job reads A's offsets through a pointer), B queued and taken (A parks in
+// B's slot), A borrowed back for its last hand-off and returned, C queued into
+// the slot that holds A, C taken.
+void submit_sequence() {
+  const std::vector<int64_t> off_a = {0, 5000, 9000}, off_b = {0, 100, 300, 600, 7000}, off_c = {0, 40000};
+  {
+    Ctx cur;
+    Batch slot[2];
+    fill_batch(cur, off_a, 11.0);
+    cur.grid = {1, 0};
+    cur.cached = true;  // a synchronous load leaves the device buffer mirrored on the host
+    const int64_t* job = cur.off.data();  // PipeJob::offsets of A's job
+    void* pts_a = cur.pts.p;
+    auto job_reads_a = [&] { return job[0] == off_a[0] && job[1] == off_a[1] && job[2] == off_a[2]; };
+
+    fill_batch(slot[0], off_b, 22.0);
+    void* pts_b = slot[0].pts.p;
+    const int frees0 = CountingMem::frees;
+    cur.swap_batch(slot[0]);  // take_staged: B current, A parked, whole
+    CHECK(cur.n == 4 && cur.maxabs == 22.0 && cur.pts.p == pts_b && cur.off == off_b && cur.grid.empty());
+    CHECK(slot[0].n == 2 && slot[0].maxabs == 11.0 && slot[0].pts.p == pts_a && slot[0].grid.size() == 2);
+    CHECK(!cur.cached && !slot[0].cached);
+    CHECK(slot[0].off.data() == job && job_reads_a());
+    const int64_t* job_b = cur.off.data();
+
+    cur.swap_batch(slot[0]);  // A's last hand-off: A borrowed back, every field its own
+    CHECK(cur.n == 2 && cur.maxabs == 11.0 && cur.pts.p == pts_a && cur.off.data() == job && cur.grid.size() == 2);
+    CHECK(slot[0].n == 4 && slot[0].pts.p == pts_b && slot[0].off.data() == job_b);
+    CHECK(!cur.cached && !slot[0].cached && job_reads_a());
+    cur.swap_batch(slot[0]);  // ... and returned
+    CHECK(cur.n == 4 && cur.maxabs == 22.0 && cur.pts.p == pts_b && cur.off.data() == job_b);
+    CHECK(slot[0].pts.p == pts_a && slot[0].off.data() == job && job_reads_a());
+    CHECK(!cur.cached && !slot[0].cached);
+    CHECK(CountingMem::frees == frees0 && CountingMem::live.size() == 2);  // swaps free nothing
+
+    // A's job is complete: the next batch is queued into the slot that holds A (its points outgrow A's buffer)
+    fill_batch(slot[0], off_c, 33.0);
+    CHECK(CountingMem::frees == frees0 + 1 && CountingMem::live.size() == 2 && slot[0].pts.cap == 640000);
+    void* pts_c = slot[0].pts.p;
+    cur.swap_batch(slot[0]);  // C taken: B parks where A did
+    CHECK(cur.n == 1 && cur.maxabs == 33.0 && cur.pts.p == pts_c && cur.off == off_c && cur.grid.empty());
+    CHECK(slot[0].n == 4 && slot[0].pts.p == pts_b && slot[0].off.data() == job_b && slot[0].off == off_b);
+    CHECK(!cur.cached && !slot[0].cached);
+    CHECK(slot[1].pts.p == nullptr && slot[1].n == -1);
+  }
+  CHECK(CountingMem::balanced());
+}
+
 }  // namespace
 
 int main() {
@@ -207,6 +286,7 @@ int main() {
   failures();
   moves();
   eviction();
+  submit_sequence();
   std::printf("allocs=%d frees=%d bad_frees=%d live=%zu failed=%d\n", CountingMem::allocs, CountingMem::frees,
               CountingMem::bad_frees, CountingMem::live.size(), g_failed);
   if (g_failed || !CountingMem::balanced()) return 1;

@@ -30,8 +30,8 @@ ONE = {"CSM_PIPELINE": "16", "CSM_PIPELINE_PARTS": "2", "CSM_FIRST_WINDOWS": "0"
 FULL = 1 << 20  # a beam count: the scan as it is
 
 
-# ---- the driver's split and window order, restated (csm_driver.cpp job_setup, window_order,
-# level_begin_split, level_end_begin) -------------------------------------------------------
+# ---- the driver's split and window order, restated (csm_pipeline.cpp job_setup, window_order;
+# csm_level.cpp level_begin_split, level_end_begin) -----------------------------------------
 
 def _parts(n, permille=550):
     """job_setup, two parts: part 0 takes permille of the scans (550; 500 for submitted batches)."""

@@ -1225,6 +1225,64 @@ def test_submitted_batches_of_varied_sizes(world2000):
             p.close()
 
 
+def test_submitted_batches_of_permuted_scans(world2000):
+    """Queued batches submitted back to back, each the same 64 scans in another
+    order and at another scale: the scan count and the point total stay, every
+    offset and the points' extent change from one batch to the next, so a batch
+    matched on another batch's offsets, points or bound (the parked batch
+    borrowed back for its deferred last hand-off travels whole) reads inside
+    every buffer and differs. Every batch equals its own synchronous load +
+    match bit for bit."""
+    import roborts_csm
+    from roborts_csm.params import headline_levels
+    w, b = world2000
+    env = {"CSM_PIPELINE": "16", "CSM_PIPELINE_PARTS": "2"}
+    os.environ.update(env)
+    try:
+        c = roborts_csm.Context(0)
+    finally:
+        for k in env:
+            del os.environ[k]
+    lv = headline_levels()
+    n = 64
+    rng = np.random.default_rng(17)
+    lens = np.diff(b.offsets[:n + 1])
+    assert len(set(lens.tolist())) > 8  # the orders give different offsets
+    batches = []
+    for f in (1.0, 0.98, 1.02, 0.99):
+        order = rng.permutation(n)
+        pts = np.concatenate([b.points_cells[b.offsets[s]:b.offsets[s + 1]] for s in order]) * f
+        off = np.concatenate([[0], np.cumsum(lens[order])]).astype(np.int64)
+        batches.append((np.ascontiguousarray(pts), off, np.ascontiguousarray(b.init_poses[order])))
+    assert all(not np.array_equal(batches[k][1], batches[k + 1][1]) for k in range(len(batches) - 1))
+    eye = np.tile(np.eye(3).reshape(1, 9), (n, 1))
+    pins = []
+    try:
+        c.set_grid(_map(w.grid, w.resolution, w.offset, version=1))
+        want = []
+        for q, off, init in batches:
+            c.load_scans(q, off)
+            p, cv = init.copy(), eye.copy()
+            want.append((c.scan_matchers_loaded(lv, p, cv), p, cv))
+        for q, _, _ in batches:
+            pins.append(roborts_csm.PinnedArray(q.shape))
+            np.copyto(pins[-1].array, q)
+        got = [(np.zeros(n), init.copy(), eye.copy()) for _, _, init in batches]
+        c.load_scans_async(pins[0].array, batches[0][1])
+        for k in range(len(batches)):
+            if k + 1 < len(batches):
+                c.load_scans_async(pins[k + 1].array, batches[k + 1][1])
+            c.scan_matchers_submit(lv, got[k][1], got[k][2], got[k][0])
+        c.scan_matchers_wait()
+        for k in range(len(batches)):
+            for a, e in zip(got[k], want[k]):
+                assert np.array_equal(a, e), k
+    finally:
+        c.close()
+        for p in pins:
+            p.close()
+
+
 @pytest.fixture(scope="module")
 def world2000_bench():
     """The bench's own config-2 inputs: the seeded 2000 x 2000 world and

@@ -8,7 +8,14 @@ std::swap and the eviction pattern (an empty value assigned over a slot that
 holds buffers; a struct of buffers and scalars standing in for GridState,
 swapped whole) end with every allocation freed exactly once and none live.
 A move assignment that does not free its target fails it (tried: moves(),
-eviction() and the final balance report it). The same program once more under
+eviction() and the final balance report it). submit_sequence() runs
+csm_scan_matchers_submit's exchanges on a stand-in for ScanBatch: a loaded
+batch whose job reads its offsets through a pointer, a queued batch taken (one
+whole swap), the parked batch borrowed back and returned, the next batch
+queued into the slot that holds the parked one, and that one taken; the
+pointer addresses the first batch's offsets, unchanged, until its slot is
+queued into, every field travels with its batch, the cache flag is false after
+every swap and each allocation is freed once. The same program once more under
 ASan + UBSan, stand-alone. No GPU."""
 import os
 import re
@@ -35,8 +42,8 @@ def _check(out):
     assert "resources_check ok" in out, out[-2000:]
     f = {k: int(v) for k, v in re.findall(r"(\w+)=(\d+)", out.splitlines()[-2])}
     assert f["failed"] == 0 and f["live"] == 0 and f["bad_frees"] == 0
-    # 7 in sizes(), 1 in failures(), 3 in moves(), 16 in eviction()
-    assert f["allocs"] == f["frees"] == 27
+    # 7 in sizes(), 1 in failures(), 3 in moves(), 16 in eviction(), 3 in submit_sequence()
+    assert f["allocs"] == f["frees"] == 30
 
 
 def test_buffer_owns_what_it_allocates(tmp_path):

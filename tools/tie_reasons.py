@@ -32,7 +32,7 @@ KCAP, KCOV = 128, 20
 
 
 def lists(levels, l):
-    """(want_pos, want_ang) of level l: live_lists (csm_driver.cpp) | own_lists_skip (csm_host_finish.cpp)."""
+    """(want_pos, want_ang) of level l: live_lists (csm_level.cpp) | own_lists_skip (csm_host_finish.cpp)."""
     pos = lambda t: t in (COARSE, FINE)  # noqa: E731 (FAST not used here)
     ang = lambda t: t in (COARSE, SUPER)  # noqa: E731
     skip = 0
