@@ -584,6 +584,87 @@ int csm_search_bounds(csm_ctx* ctx, const double* points_xy, int32_t n_points,
                       const double* centers_map, int32_t depth, int32_t kernel,
                       double* bounds, int64_t* sums, int64_t n_out);
 
+/* --- the full ScanMatch result from the admissible search ------------------- */
+/* BasedCorrelationScanMatch::ScanMatch (correlate_scan_matcher.h:784-875) for
+ * the best of n_windows windows, without scoring the window exhaustively: what
+ * RangeScanPoseGraph::TryCloseLoop reads of a loop match
+ * (pose_graph/range_scan_pose_graph.cpp:299-355) -- the response it gates on,
+ * covariance(0,0) and (1,1) it gates on, and best_pose / covariance it hands
+ * to LinkChainToScan; best_pose is FindBestCandidate's score-weighted average
+ * over the tied prefix (:670-710), not the argmax.
+ *
+ * Phase 1 is csm_search_windows: the winner window and its argmax, same tie
+ * rule. Phase 2: with s* the best score and T = std::min(s* - 0.1, 0.5)
+ * (:912, :986), everything the finish reads lies in {s >= T}: FindBest's
+ * prefix s >= s* - 0.01 (:676), ComputePositionalCovariance's first 20 sorted
+ * candidates with s > T (:915-928), ComputeAngularCovariance's with s >= T
+ * (:990-1003). The pooled levels bound every node from above (and the raw
+ * bound bounds the penalised score: the penalty factor lies in [0.45, 1]), so
+ * the same descent with the fixed threshold T in place of the incumbent
+ * enumerates that set exactly; the host sorts it and finishes as the
+ * reference does (:835-869). Where std::sort's order among equal scores could
+ * change an output, or the set outgrows collect_capacity, the winner window is
+ * scored exhaustively and finished as csm_scan_match finishes it: the result
+ * is the reference's either way, never approximate. */
+typedef struct csm_match_options {
+  csm_search_options search;  /* phase 1 (and the collect's top depth, list capacity, top kernel) */
+  int64_t collect_capacity;   /* candidates the collected list holds (0: 10240, the exact finish's
+                                 window size); more candidates at or above T: path 2 */
+  double min_response;        /* best < min_response: path 4, no phase 2 (TryCloseLoop rejects on
+                                 the response first; a low best makes T low and the set large).
+                                 0: never skip */
+} csm_match_options;
+
+enum csm_match_path {
+  CSM_MATCH_PRUNED = 0,         /* collected set, sorted and finished on the host              */
+  CSM_MATCH_TIE = 1,            /* exhaustive: a tie among equal scores matters                */
+  CSM_MATCH_OVERFLOW = 2,       /* exhaustive: more than collect_capacity candidates reach T   */
+  CSM_MATCH_UNPOOLED = 3,       /* exhaustive: the windows are outside the pooled search
+                                   (csm_search_stats.exhaustive = 1)                           */
+  CSM_MATCH_LOW_RESPONSE = 4,   /* skipped by min_response                                     */
+  CSM_MATCH_NO_RESPONSE = 5     /* best < 1e-6: the covariances' early return (:894-899,
+                                   :973-976), no collect                                       */
+};
+
+typedef struct csm_match_result {
+  double response;          /* the best score clamped to 1 (:861-863)                            */
+  double pose_map[3];       /* best_pose in the winner's map cells / rad; always written. Paths
+                               0-3: FindBestCandidate's averaged pose. Paths 4 and 5: the argmax
+                               candidate's pose (no finish ran)                                   */
+  int32_t accepted;         /* response > param->response_threshold (:866); 0 on paths 4 and 5  */
+  int32_t window;           /* the winner                                                        */
+  csm_best front;           /* the candidate sorted first (paths 4, 5: phase 1's argmax)         */
+  int32_t count;            /* FindBestCandidate's prefix length (0 on paths 4 and 5)            */
+  int32_t path;             /* enum csm_match_path                                               */
+  double threshold;         /* T (paths 4, 5: what it would have been)                           */
+  int64_t collected;        /* candidates with score >= T the collect found (0: no collect ran)  */
+  csm_search_stats search;  /* phase 1                                                           */
+  int64_t collect_nodes[11];/* nodes the collect bounded at each level ([0]: leaves scored)      */
+} csm_match_result;
+
+/* Windows as csm_search_windows; centres and pose_map in map cells / rad
+ * (offsets stay with the caller). cov: row-major 3x3 in/out, written per type
+ * exactly as csm_scan_match writes it (:835-858: COARSE both covariances,
+ * FINE the positional, SUPER the angular one); untouched on path 4. Path 5 is
+ * taken only when the response is not accepted (a negative threshold goes
+ * through the collect). param->type == CSM_FAST: CSM_ERR_INVALID_ARG.
+ * kernel_stats: "pyr_collect" (the collect's descent) and
+ * "search_match:exhaustive" (launches = the count of fallbacks). */
+int csm_search_match(csm_ctx* ctx, const double* points_xy, int32_t n_points, const csm_param* param,
+                     int32_t n_windows, const int32_t* grid_index, const double* centers_map,
+                     const csm_match_options* options, double cov[9], csm_match_result* result);
+
+/* Test hook: the collected set of one window (on grid grid_index of the
+ * stack, centred at center_map) at a given threshold and top depth (0..10):
+ * every candidate with score >= threshold (the set phase 2 of
+ * csm_search_match sorts, :912/:986's bound in place of `threshold`), as (flat
+ * index, score) in ascending flat order. *n_found counts all of them; at most
+ * `capacity` are written. CSM_ERR_UNSUPPORTED when the window is outside the
+ * pooled search. */
+int csm_search_collect(csm_ctx* ctx, const double* points_xy, int32_t n_points, const csm_param* param,
+                       int32_t grid_index, const double center_map[3], int32_t depth, double threshold,
+                       int64_t* flat, double* score, int64_t capacity, int64_t* n_found);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,22 @@ int csm_loop_closure_match(csm_loop_closure* lc, const double* points_xy, int32_
                            const csm_param* param, const double pose_world[3], int32_t search,
                            csm_loop_closure_result* result);
 
+/* csm_loop_closure_match, then the full ScanMatch result of the winning
+ * submap's window -- what TryCloseLoop gates on and hands to LinkChainToScan
+ * (pose_graph/range_scan_pose_graph.cpp:299-355: response, covariance(0,0) and
+ * (1,1), best_pose, covariance). The match and the exchange run unchanged;
+ * then the device that holds the winning submap runs csm_search_match on that
+ * one window of its resident stack (default options; the pooled levels are
+ * cached there). result: every field as csm_loop_closure_match fills it,
+ * except pose_world = GetWorldCoordsPose (grid_map_base.h:83-87) of
+ * match->pose_map, FindBestCandidate's averaged pose
+ * (correlate_scan_matcher.h:670-710), with the submap's offset. match->window
+ * is the submap. cov: row-major 3x3 in/out, as csm_search_match writes it.
+ * param->type == CSM_FAST: CSM_ERR_INVALID_ARG. */
+int csm_loop_closure_match_full(csm_loop_closure* lc, const double* points_xy, int32_t n_points,
+                                const csm_param* param, const double pose_world[3], int32_t search,
+                                double cov[9], csm_loop_closure_result* result, csm_match_result* match);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@
 #include "csm_resources.hpp"
 #include "host_math.hpp"
 #include "csm_pyramid.hpp"
+#include "csm_search_match.hpp"
 #include "csm_level_decision.hpp"
 
 #include <algorithm>
@@ -63,8 +64,8 @@ using csm::ScanWork;
 struct csm_ctx;
 
 namespace csmh {
-constexpr double kMaxVariance = 500.0;      // util/slam_util.h:57
-constexpr double kDoubleTolerance = 1e-06;  // util/slam_util.h:59
+using csm::kMaxVariance;      // util/slam_util.h:57 (csm_search_match.hpp)
+using csm::kDoubleTolerance;  // util/slam_util.h:59
 constexpr int kMaxVarianceUsePointSize = 20;       // correlate_scan_matcher.h:1033
 
 inline bool double_equal(double a, double b, double tol = kDoubleTolerance) {

@@ -114,81 +114,11 @@ uint32_t read_sealed(const csm::FinishOut* src, int32_t tag, csm::FinishOut& out
 
 double complete_window(const csm::FinishOut& o, const CandGeom& C, const csm_param& P,
                        const Geometry& G, double pose[3], double cov[9], int skip_lists) {
-  const double best_score = o.best_score;
-  const double best_x = o.best_x, best_y = o.best_y;
-  double best_a = C.a(o.front_idx).angle;
-  if (o.count > 1) best_a = std::atan2(o.thy / o.ssum, o.thx / o.ssum);  // :702-706
-
-  const double sres = P.search_space_resolution;
-  const double max_ang_var = 4 * (P.search_angle_resolution * P.search_angle_resolution);  // :801
-
-  auto positional = [&]() {  // ComputePositionalCovariance (:887-956)
-    for (int i = 0; i < 9; ++i) cov[i] = (i % 4 == 0) ? 1.0 : 0.0;
-    if (best_score < kDoubleTolerance) {
-      cov[0] = kMaxVariance;
-      cov[4] = kMaxVariance;
-      cov[8] = max_ang_var;
-      return;
-    }
-    double vxx = 0.0, vxy = 0.0, vyy = 0.0, norm = 0.0;
-    for (int i = 0; i < o.n_pos; ++i) {
-      const double sc = o.pos_score[i];
-      const double dx = C.x(o.pos_idx[i]) - best_x, dy = C.y(o.pos_idx[i]) - best_y;
-      norm += sc;
-      vxx += (dx * dx * sc);
-      vxy += (dx * dy * sc);
-      vyy += (dy * dy * sc);
-    }
-    if (norm > kDoubleTolerance) {
-      double xx = vxx / norm, xy = vxy / norm, yy = vyy / norm;
-      const double r = sres / G.mres;
-      const double minv = 0.1 * (r * r);
-      xx = std::max<double>(xx, minv);
-      yy = std::max<double>(yy, minv);
-      const double m2 = G.mres * G.mres;
-      cov[0] = (xx * m2) / best_score;
-      cov[1] = (xy * m2) / best_score;
-      cov[3] = (xy * m2) / best_score;
-      cov[4] = (yy * m2) / best_score;
-      cov[8] = max_ang_var;
-    }
-    if (double_equal(cov[0], 0.0)) cov[0] = kMaxVariance;
-    if (double_equal(cov[4], 0.0)) cov[4] = kMaxVariance;
-  };
-  auto angular = [&]() {  // ComputeAngularCovariance (:965-1019)
-    if (best_score < kDoubleTolerance) {
-      cov[8] = max_ang_var;
-      return;
-    }
-    double norm = 0.0, acc = 0.0;
-    for (int i = 0; i < o.n_ang; ++i) {
-      const double sc = o.ang_score[i];
-      const double d = C.a(o.ang_idx[i]).angle - best_a;
-      norm += sc;
-      acc += (d * d * sc);
-    }
-    cov[8] = (norm > kDoubleTolerance) ? acc / norm : 200 * max_ang_var;
-  };
-  const bool pos = !(skip_lists & 1), ang = !(skip_lists & 2);
-  switch (P.type) {
-    case CSM_COARSE:
-      if (pos) positional();
-      if (ang) angular();
-      break;
-    case CSM_FINE:
-      if (pos) positional();
-      break;
-    case CSM_SUPER:
-      if (ang) angular();
-      break;
-    default:
-      break;
-  }
-  const double response = best_score > 1.0 ? 1.0 : best_score;  // :861-863
-  if (response > P.response_threshold) {                        // :866-869
-    const double bp[3] = {best_x, best_y, best_a};
-    G.to_world(bp, pose);
-  }
+  // the best pose, the covariances and the response: csm_search_match.cpp
+  const csm::FinishWindow W{C.grid(), C.angles, P.type, G.mres, P.search_space_resolution, P.search_angle_resolution};
+  double bp[3];
+  const double response = csm::finish_complete(o, W, skip_lists, bp, cov);
+  if (response > P.response_threshold) G.to_world(bp, pose);  // :866-869
   return response;
 }
 

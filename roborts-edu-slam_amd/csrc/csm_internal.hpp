@@ -213,6 +213,13 @@ struct BestPartial {
   int64_t flat;
 };
 
+// A candidate the admissible search's collect keeps (csm_pyramid.hpp): its
+// exact score and flat index.
+struct PyrHit {
+  double score;
+  int64_t flat;
+};
+
 constexpr int kBlock = 256;      // 4 waves
 constexpr int kChunk = 1024;     // beams staged in LDS per pass (16 KB)
 

@@ -289,11 +289,9 @@ int csm_loop_closure_set_submaps(csm_loop_closure* lc, const float* cells, int32
   return CSM_OK;
 }
 
-int csm_loop_closure_match(csm_loop_closure* lc, const double* pts, int32_t n_points, const csm_param* param,
+// csm_loop_closure_match with lc->mu held.
+static int lc_match_locked(csm_loop_closure* lc, const double* pts, int32_t n_points, const csm_param* param,
                            const double pose_world[3], int32_t search, csm_loop_closure_result* res) {
-  if (!lc || !pts || !param || !pose_world || !res) return CSM_ERR_INVALID_ARG;
-  if (search != CSM_LC_PYRAMID && search != CSM_LC_EXHAUSTIVE) return CSM_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(lc->mu);
   DeviceRestore restore;
   if (lc->broken) return lc->fail(CSM_ERR_HIP, "an earlier exchange failed part-way: the communicators are out of step");
   if (lc->n_submaps == 0) return lc->fail(CSM_ERR_NO_GRID, "no submaps set");
@@ -448,6 +446,47 @@ int csm_loop_closure_match(csm_loop_closure* lc, const double* pts, int32_t n_po
     res->pose_world[1] = inv_a * res->y + nty;
     res->pose_world[2] = res->angle;
   }
+  return CSM_OK;
+}
+
+int csm_loop_closure_match(csm_loop_closure* lc, const double* pts, int32_t n_points, const csm_param* param,
+                           const double pose_world[3], int32_t search, csm_loop_closure_result* res) {
+  if (!lc || !pts || !param || !pose_world || !res) return CSM_ERR_INVALID_ARG;
+  if (search != CSM_LC_PYRAMID && search != CSM_LC_EXHAUSTIVE) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(lc->mu);
+  return lc_match_locked(lc, pts, n_points, param, pose_world, search, res);
+}
+
+int csm_loop_closure_match_full(csm_loop_closure* lc, const double* pts, int32_t n_points, const csm_param* param,
+                                const double pose_world[3], int32_t search, double cov[9],
+                                csm_loop_closure_result* res, csm_match_result* match) {
+  if (!lc || !pts || !param || !pose_world || !cov || !res || !match) return CSM_ERR_INVALID_ARG;
+  if (search != CSM_LC_PYRAMID && search != CSM_LC_EXHAUSTIVE) return CSM_ERR_INVALID_ARG;
+  if (param->type == CSM_FAST) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(lc->mu);
+  int st = lc_match_locked(lc, pts, n_points, param, pose_world, search, res);
+  if (st != CSM_OK) return st;
+  if (res->submap < 0) return lc->fail(CSM_ERR_INVALID_ARG, "no submap was scored");
+  // the device that holds the winning submap finishes that one window on its
+  // resident stack (its pooled levels are the ones the search just used)
+  const int G = (int)lc->devices.size();
+  int r = 0;
+  while (r < G - 1 && !(res->submap >= lc->lo[(size_t)r] && res->submap < lc->hi[(size_t)r])) ++r;
+  const int32_t local = res->submap - lc->lo[(size_t)r];
+  const double s = 1.0 / lc->resolution;
+  const double tx = s * lc->offsets[2 * (size_t)res->submap], ty = s * lc->offsets[2 * (size_t)res->submap + 1];
+  const double center[3] = {s * pose_world[0] + tx, s * pose_world[1] + ty, pose_world[2]};  // GetMapCoordsPose, as the match
+  DeviceRestore restore;
+  st = csm_search_match(lc->ctx[(size_t)r], pts, n_points, param, 1, &local, center, nullptr, cov, match);
+  if (st != CSM_OK)
+    return lc->fail(st, "device " + std::to_string(lc->devices[(size_t)r]) + ": " + csm_last_error(lc->ctx[(size_t)r]));
+  match->window = res->submap;  // the winner among all submaps
+  // GetWorldCoordsPose of the averaged pose in its submap (grid_map_base.h:83-87)
+  const double inv_a = s * (1.0 / (s * s - 0.0 * 0.0));
+  const double ntx = -(inv_a * tx), nty = -(inv_a * ty);
+  res->pose_world[0] = inv_a * match->pose_map[0] + ntx;
+  res->pose_world[1] = inv_a * match->pose_map[1] + nty;
+  res->pose_world[2] = match->pose_map[2];
   return CSM_OK;
 }
 

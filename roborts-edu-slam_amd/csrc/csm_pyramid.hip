@@ -244,6 +244,99 @@ __global__ __launch_bounds__(kPB) void pyr_bound_kernel(LevelWork L, PyrGrid lev
   block_best(bv, bf, bn, partials + blockIdx.x);
 }
 
+// Collect mode's depth 0 (PyramidSearch::collect): pyr_bound_kernel's exact
+// candidate score at d = 0 -- the same beam staging, gathers, lanes per node
+// and penalised score -- but in place of the block's best every leaf with
+// score >= T is appended to `out` as (score, flat index). A wave's lanes step
+// through the list together (its 64 / lpn nodes per pass), so the append is
+// wave-wide: a ballot of the hits, one returning atomic per wave for their
+// number, each hit's slot from its rank in the ballot. *count takes every hit;
+// only slots below cap are written. Invalid nodes (kPyrNoNode, J or K outside
+// the window) append nothing.
+__global__ __launch_bounds__(kPB) void pyr_collect_kernel(LevelWork L, PyrGrid lev,
+                                                          const ScanWork* __restrict__ scans,
+                                                          const AngleEntry* __restrict__ angles,
+                                                          const double2* __restrict__ pts, int32_t n_used,
+                                                          int32_t step, const uint64_t* __restrict__ nodes,
+                                                          int64_t n_host, const unsigned long long* __restrict__ n_dev,
+                                                          double T, PyrHit* __restrict__ out,
+                                                          unsigned long long* __restrict__ count, int64_t cap,
+                                                          unsigned long long* __restrict__ scored) {
+  extern __shared__ double2 beams[];
+  const int64_t n = n_dev ? (int64_t)*n_dev : n_host;
+  const int64_t threads = (int64_t)gridDim.x * kPB;
+  int lpn = 1, lpn_lg = 0;  // a power of two, the same in every block (pyr_bound_kernel's rule)
+  while (lpn < 64 && n * (2 * lpn) <= threads && 2 * lpn <= n_used) {
+    lpn <<= 1;
+    ++lpn_lg;
+  }
+  if (((int64_t)blockIdx.x * kPB) / lpn >= n) return;  // no node for this block (uniform)
+  for (int b = threadIdx.x; b < n_used; b += kPB) beams[b] = pts[(int64_t)b * step];
+  __syncthreads();
+  if (scored && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(scored, (unsigned long long)n);
+  const int W = lev.width, H = lev.height, pitch = lev.pitch;
+  const int lane = threadIdx.x & 63;
+  const int sub = lane & (lpn - 1);
+  const int32_t* __restrict__ g0 = (const int32_t*)lev.g;
+  // the wave's first node: uniform, so every lane of the wave makes every pass
+  for (int64_t base = ((int64_t)blockIdx.x * kPB + (threadIdx.x & ~63)) >> lpn_lg; base < n; base += threads >> lpn_lg) {
+    const int64_t i = base + (lane >> lpn_lg);
+    const uint64_t nd = i < n ? nodes[i] : kPyrNoNode;
+    int w, a, J, K;
+    node_decode(nd, w, a, J, K);
+    const bool valid = nd != kPyrNoNode && w < L.n_scans && a < L.n_angles && J < L.n_space && K < L.n_space;
+    int64_t sum = 0;
+    if (valid) {
+      const ScanWork S = scans[w];
+      const AngleEntry ae = angles[S.angle_off + a];
+      const double x = S.x0 + J * L.step_cells;  // :569
+      const double y = S.y0 + K * L.step_cells;  // :572
+      const int32_t* __restrict__ g = g0 + (int64_t)S.grid_index * lev.stride;
+      auto cell = [&](int b) -> int32_t {
+        const double2 p = beams[b];
+        const double lx = ae.cosine * p.x - ae.sine * p.y;
+        const double ly = ae.sine * p.x + ae.cosine * p.y;
+        const int gx = (int)((lx + x) + 0.5);
+        const int gy = (int)((ly + y) + 0.5);
+        const bool in = (unsigned)gx < (unsigned)W && (unsigned)gy < (unsigned)H;
+        const int32_t c = g[in ? (int64_t)gy * pitch + gx : 0];
+        return in ? c : 0;
+      };
+      int b = sub;
+      for (; b + 7 * lpn < n_used; b += 8 * lpn) {  // 8 gathers in flight per lane
+        int32_t c[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) c[u] = cell(b + u * lpn);
+        // |c| < 2^26: eight fit an int32
+        sum += (int64_t)(((c[0] + c[1]) + (c[2] + c[3])) + ((c[4] + c[5]) + (c[6] + c[7])));
+      }
+      for (; b < n_used; b += lpn) sum += cell(b);
+    }
+    for (int o = lpn / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);  // the node's lanes (all valid or none)
+    double v = 0.0;
+    int64_t flat = 0;
+    bool hit = false;
+    if (valid && sub == 0) {
+      const ScanWork S = scans[w];
+      const AngleEntry ae = angles[S.angle_off + a];
+      const double x = S.x0 + J * L.step_cells;  // :569
+      const double y = S.y0 + K * L.step_cells;  // :572
+      v = penalized(L, S, dev::fixed_point_acc(L, sum, n_used), x, y, ae.angle);
+      flat = (int64_t)w * L.n_cand + ((int64_t)a * L.n_space + J) * L.n_space + K;
+      hit = v >= T;
+    }
+    const uint64_t m = __builtin_amdgcn_ballot_w64(hit);
+    if (m == 0) continue;  // uniform
+    unsigned long long first = 0;
+    if (lane == 0) first = atomicAdd(count, (unsigned long long)__builtin_popcountll(m));
+    first = __shfl(first, 0, 64);
+    if (hit) {
+      const int64_t o = (int64_t)first + __builtin_popcountll(m & (((uint64_t)1 << lane) - 1));
+      if (o < cap) out[o] = PyrHit{v, flat};
+    }
+  }
+}
+
 // The whole top level at once, laid out as the exhaustive column kernel
 // (csm_kernels.hip score_cols_kernel): lane = one (angle, J) column of a
 // window, kt rows K per lane, so a beam's rotation and column are computed
@@ -785,8 +878,8 @@ __global__ __launch_bounds__(256) void pyr_expand_kernel(LevelWork L, int d, con
 // A search's device state at its start: the incumbent at "none", the node
 // counters zero (one launch in place of a copy and a memset).
 __global__ __launch_bounds__(256) void pyr_init_kernel(BestPartial* __restrict__ inc,
-                                                       unsigned long long* __restrict__ zero, int n) {
-  if (threadIdx.x == 0) *inc = BestPartial{-1.7976931348623157e308, INT64_MAX};  // {-DBL_MAX, INT64_MAX}
+                                                       unsigned long long* __restrict__ zero, int n, double start) {
+  if (threadIdx.x == 0) *inc = BestPartial{start, INT64_MAX};  // a search: {-DBL_MAX, INT64_MAX}
   for (int i = threadIdx.x; i < n; i += blockDim.x) zero[i] = 0;
 }
 
@@ -846,6 +939,19 @@ hipError_t launch_pyr_bound(const LevelWork& L, const PyrGrid& lev, int d, const
   else
     hipLaunchKernelGGL(pyr_bound_kernel<int16_t>, dim3(blocks), dim3(kPB), lds, stream, L, lev, d, scans, angles, p,
                        n_used, step, nodes, n, n_dev, vals, partials, scored);
+  return hipGetLastError();
+}
+
+hipError_t launch_pyr_collect(const LevelWork& L, const PyrGrid& lev0, const ScanWork* scans, const AngleEntry* angles,
+                              const double* pts, int32_t n_used, int32_t step, const uint64_t* nodes, int64_t n,
+                              const unsigned long long* n_dev, int64_t upper, double T, PyrHit* out,
+                              unsigned long long* count, int64_t cap, unsigned long long* scored,
+                              hipStream_t stream) {
+  if (upper <= 0) return hipSuccess;
+  if (lev0.qs != 0 || lev0.lg != 0 || lev0.shift != 0) return hipErrorInvalidValue;  // the fixed-point grid itself
+  hipLaunchKernelGGL(pyr_collect_kernel, dim3((unsigned)pyr_bound_blocks(upper, n_used)), dim3(kPB),
+                     (size_t)n_used * sizeof(double2), stream, L, lev0, scans, angles,
+                     reinterpret_cast<const double2*>(pts), n_used, step, nodes, n, n_dev, T, out, count, cap, scored);
   return hipGetLastError();
 }
 
@@ -950,8 +1056,8 @@ hipError_t launch_pyr_expand_top(const LevelWork& L, int d, int32_t nj, int qs, 
   return hipGetLastError();
 }
 
-hipError_t launch_pyr_init(BestPartial* inc, unsigned long long* zero, int n, hipStream_t stream) {
-  hipLaunchKernelGGL(pyr_init_kernel, dim3(1), dim3(256), 0, stream, inc, zero, n);
+hipError_t launch_pyr_init(BestPartial* inc, unsigned long long* zero, int n, hipStream_t stream, double start) {
+  hipLaunchKernelGGL(pyr_init_kernel, dim3(1), dim3(256), 0, stream, inc, zero, n, start);
   return hipGetLastError();
 }
 

@@ -76,8 +76,10 @@ int pyr_blocks(int64_t upper);
 // writes (<= pyr_blocks's cap); the kernel spreads each node over up to a
 // wave of lanes when the list is short.
 int pyr_bound_blocks(int64_t upper, int32_t n_used);
-// A search's start: *inc = {-DBL_MAX, INT64_MAX}, zero[0, n) = 0.
-hipError_t launch_pyr_init(BestPartial* inc, unsigned long long* zero, int n, hipStream_t stream);
+// A search's start: *inc = {start, INT64_MAX} (a search: -DBL_MAX; a collect:
+// its threshold), zero[0, n) = 0.
+hipError_t launch_pyr_init(BestPartial* inc, unsigned long long* zero, int n, hipStream_t stream,
+                           double start = -1.7976931348623157e308);
 // Bounds (d >= 1) or exact scores (d = 0) of the nodes; one best per block
 // into partials (pyr_bound_blocks(upper, n_used) entries); *scored (nullable) += the count. The windows share one scan: its
 // n_used beams (stride step from pts) are staged in LDS.
@@ -85,6 +87,16 @@ hipError_t launch_pyr_bound(const LevelWork& L, const PyrGrid& lev, int d, const
                             const AngleEntry* angles, const double* pts, int32_t n_used, int32_t step,
                             const uint64_t* nodes, int64_t n, const unsigned long long* n_dev, int64_t upper,
                             double* vals, PyrPartial* partials, unsigned long long* scored, hipStream_t stream);
+// Collect mode's depth 0: the exact scores of depth-0 nodes as launch_pyr_bound
+// computes them (lev0: the fixed-point grid); every leaf with score >= T is
+// appended to out[*count] as (score, flat index), one atomic per wave. *count
+// takes every such leaf, only slots below cap are written; invalid nodes
+// append nothing. *scored (nullable) += the count of nodes.
+hipError_t launch_pyr_collect(const LevelWork& L, const PyrGrid& lev0, const ScanWork* scans, const AngleEntry* angles,
+                              const double* pts, int32_t n_used, int32_t step, const uint64_t* nodes, int64_t n,
+                              const unsigned long long* n_dev, int64_t upper, double T, PyrHit* out,
+                              unsigned long long* count, int64_t cap, unsigned long long* scored,
+                              hipStream_t stream);
 // The whole top level in one launch (all windows, angles, J, K): nodes and
 // bounds in list order, one best per block (pyr_top_blocks of them; -1 when
 // the grid would not fit a launch).
@@ -149,6 +161,9 @@ struct PyrStats {
   int32_t bound_launches[kPyrMaxDepth + 1] = {};
   double bound_ms[kPyrMaxDepth + 1] = {};
   double build_ms = 0.0;                 // pooled levels built (0 when cached)
+  // PyramidSearch::collect: the nodes it bounded per depth (0: leaves scored
+  // exactly); run leaves them zero, collect writes nothing else
+  int64_t collect_nodes[kPyrMaxDepth + 1] = {};
 };
 
 struct PyrInputs {
@@ -186,6 +201,18 @@ class PyramidSearch {
   // or reused as run does; the buffers are the hook's own.
   hipError_t top_bounds(const PyrInputs& in, int kernel, double* bounds, int64_t* sums, int64_t n_out,
                         bool* unsupported, std::string* what);
+  // Collect mode: every candidate of the one window in.scans[0] (in.L.n_scans
+  // = 1: the caller passes the winner's ScanWork) whose exact score is >= T,
+  // by the same descent with the incumbent fixed at {T, INT64_MAX} and never
+  // merged, so a node survives iff bound >= T (the raw bound also bounds the
+  // penalised score); no probes; depth 0 appends its leaves
+  // (launch_pyr_collect). hits[0, min(*n_found, capacity)) in any order (host
+  // memory); *n_found counts every such candidate. The levels are the ones
+  // run built for this grid (hipErrorInvalidValue when they are not there up
+  // to in.depth): nothing is built but, at most, the top's box copy. stats
+  // (nullable): collect_nodes only.
+  hipError_t collect(const PyrInputs& in, double T, int64_t capacity, PyrHit* hits, int64_t* n_found,
+                     PyrStats* stats, std::string* what);
   // Nodes per level list (0: 4M) and the smallest level that gets an
   // incumbent probe below the top (0: 4096).
   void configure(int64_t node_capacity, int probe_min_nodes);

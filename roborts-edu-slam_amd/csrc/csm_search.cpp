@@ -21,6 +21,7 @@
 #include <chrono>
 #include <climits>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 namespace csm {
@@ -59,12 +60,21 @@ struct PyramidSearch::Impl {
   // parent list (depth d + 1) whose count that expand reads.
   static constexpr int kCountPool = 64;
   static constexpr int kCountSlots = kCountPool + kPyrMaxDepth + 1;
-  DevBuf state;  // BestPartial inc | scored[kPyrMaxDepth + 1] | pool[kCountSlots]
+  DevBuf state;  // BestPartial inc | scored[kPyrMaxDepth + 1] | pool[kCountSlots] | the collect's hit count
   int cslot[kPyrMaxDepth + 1] = {};  // pool slot of list d's count (slot 0: never written, zero)
   int next_slot = 1;
   BestPartial* inc_dev() const { return (BestPartial*)state.p; }
   unsigned long long* scored_dev() const { return (unsigned long long*)((char*)state.p + sizeof(BestPartial)); }
   unsigned long long* pool_dev() const { return scored_dev() + kPyrMaxDepth + 1; }
+  unsigned long long* hits_dev() const { return pool_dev() + kCountSlots; }
+  static constexpr int kStateWords = kPyrMaxDepth + 1 + kCountSlots + 1;  // what a search's init launch zeroes
+  // collect mode (PyramidSearch::collect): the incumbent is the threshold and
+  // is never merged, no probe runs, depth 0 appends its leaves to `hits`
+  bool collecting = false;
+  double collect_T = 0.0;
+  int64_t hit_cap = 0;
+  DevBuf hits;
+  csmh::HostBuf h_hits;
   // the beam-box top level: integer sums of the implicit node list
   DevBuf top_sums, top_thr, top_slab;
   int top_implicit = -1;  // its depth while a search runs (-1: the top is a node list)
@@ -193,9 +203,7 @@ struct PyramidSearch::Impl {
     }
     const int64_t np = ((int64_t)1 << (2 * D)) * kRoots;
     if ((e = partials.ensure_exact((size_t)pyr_blocks(INT64_MAX / 2) * sizeof(PyrPartial))) != hipSuccess) return e;
-    if ((e = state.ensure_exact(sizeof(BestPartial) + (kPyrMaxDepth + 1 + kCountSlots) * sizeof(unsigned long long))) !=
-        hipSuccess)
-      return e;
+    if ((e = state.ensure_exact(sizeof(BestPartial) + kStateWords * sizeof(unsigned long long))) != hipSuccess) return e;
     if ((e = probe_slot.ensure_exact(kRoots * sizeof(uint64_t))) != hipSuccess) return e;
     if ((e = probe_nodes.ensure_exact((size_t)np * sizeof(uint64_t))) != hipSuccess) return e;
     if ((e = probe_vals.ensure_exact((size_t)np * sizeof(double))) != hipSuccess) return e;
@@ -288,6 +296,10 @@ struct PyramidSearch::Impl {
   hipError_t level_pass(int d, int64_t n, int64_t upper, bool top) {
     hipError_t e;
     const unsigned long long* nd = n >= 0 ? nullptr : count_dev(d);
+    if (collecting && d == 0)  // the leaves at or above the threshold, appended; nothing to fold
+      return launch_pyr_collect(in.L, lev[0], in.scans, in.angles, in.pts, in.n_used, in.step,
+                                (const uint64_t*)nodes[0].p, n, nd, upper, collect_T, (PyrHit*)hits.p, hits_dev(),
+                                hit_cap, scored_dev(), in.stream);
     if ((e = bound(d, (const uint64_t*)nodes[d].p, (double*)vals[d].p, n, nd, upper)) != hipSuccess) return e;
     return descend(d, n, upper, top, pyr_bound_blocks(upper, in.n_used));
   }
@@ -299,7 +311,7 @@ struct PyramidSearch::Impl {
     if (d == 0)
       return launch_pyr_final((const PyrPartial*)partials.p, n_partials, true, 0, inc_dev(), nullptr,
                               in.stream);
-    if (probes && (top || n >= probe_min) && (e = probe(d, n_partials)) != hipSuccess) return e;
+    if (!collecting && probes && (top || n >= probe_min) && (e = probe(d, n_partials)) != hipSuccess) return e;
     const int64_t child_upper = std::min(4 * upper, possible[d - 1]);
     if (child_upper <= capd[d - 1]) {
       if ((e = expand(d, 0, n, nd, upper)) != hipSuccess) return e;
@@ -317,6 +329,88 @@ struct PyramidSearch::Impl {
       const int64_t k = std::min(slice, n - s);
       if ((e = expand(d, s, k, nullptr, k)) != hipSuccess) return e;
       if ((e = level_pass(d - 1, -1, 4 * k, false)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+
+  // A search's device state set (the incumbent at {start, INT64_MAX}), then
+  // the top level at x.depth bounded -- as beam boxes, as one whole-level
+  // launch or as node lists -- and descended. run and collect share it; what
+  // differs is the start, the probes and depth 0 (collecting). *top_scored:
+  // top nodes bounded outside the scored counters; *msg: what failed.
+  hipError_t search_levels(const PyrInputs& x, double start, int64_t* top_scored, const char** msg) {
+    hipError_t e;
+    auto bad = [&](hipError_t err, const char* m) {
+      *msg = m;
+      return err;
+    };
+    const int64_t nj = ((int64_t)x.L.n_space + (1 << x.depth) - 1) >> x.depth;
+    const int64_t n_top = (int64_t)x.L.n_scans * x.L.n_angles * nj * nj;
+    set_caps(x.L, x.depth);
+    if ((e = ensure_lists(x.depth)) != hipSuccess) return bad(e, "pyramid node lists");
+    for (int d = 0; d <= kPyrMaxDepth; ++d) cslot[d] = 0;
+    next_slot = 1;
+    if ((e = launch_pyr_init(inc_dev(), scored_dev(), kStateWords, x.stream, start)) != hipSuccess)
+      return bad(e, "pyr_init_kernel");
+    int32_t ktiles, kt, col_blocks;
+    const int top_blocks = pyr_top_blocks(x.L, (int32_t)nj, &ktiles, &kt, &col_blocks);
+    const int D = x.depth;
+    // the top level as beam boxes: one-cell steps are given; the box test
+    // needs |t| < 2^24 (box_ok), nj <= 32, a launch of n_scans * n_angles waves
+    const int npc = pyr_topbox_pieces((int32_t)nj);
+    const int64_t box_blocks = (int64_t)x.L.n_scans * x.L.n_angles;
+    const bool use_box = x.top_mode == 0 && box_eligible(x, nj, n_top);
+    if (use_box && (e = build_box(x, D, (int32_t)nj, npc)) == hipSuccess) {
+      // the split waves' partial sums: only launches of few (window, angle)s split
+      const size_t slab_ints = box_slab_ints(x, n_top);
+      if ((e = top_sums.ensure_exact((size_t)n_top * sizeof(int32_t))) != hipSuccess ||
+          (e = top_thr.ensure_exact(2 * sizeof(int64_t))) != hipSuccess ||
+          (slab_ints && (e = top_slab.ensure_exact(slab_ints * sizeof(int32_t))) != hipSuccess))
+        return bad(e, "pyramid top level");
+      if ((e = partials.ensure_exact((size_t)std::max<int64_t>(box_blocks, pyr_blocks(INT64_MAX / 2)) *
+                                 sizeof(PyrPartial))) != hipSuccess)
+        return bad(e, "pyramid partials");
+      if (x.timed && (e = mark_top(0, x.stream)) != hipSuccess) return bad(e, "hipEventRecord");
+      if ((e = launch_pyr_topbox(x.L, boxg, D, (int32_t)nj, x.scans, x.angles, x.pts, x.n_used, x.step,
+                                 (int32_t*)top_sums.p, slab_ints ? (int32_t*)top_slab.p : nullptr,
+                                 (PyrPartial*)partials.p, x.stream)) != hipSuccess)
+        return bad(e, "pyr_topbox_kernel");
+      if (x.timed) {
+        if ((e = mark_top(1, x.stream)) != hipSuccess) return bad(e, "hipEventRecord");
+        std::snprintf(st->top_name, sizeof(st->top_name), "pyr_topbox_kernel<%d,%d>", npc,
+                      (int)((nj * npc + 63) / 64));
+        st->top_bytes = (double)n_top * (double)x.n_used * 2.0;
+      }
+      *top_scored = n_top;
+      st->top_box = 1;
+      top_implicit = D;
+      top_nj = (int32_t)nj;
+      e = descend(D, n_top, n_top, true, box_blocks);
+      top_implicit = -1;
+      if (e != hipSuccess) return bad(e, "pyramid level pass");
+    } else if (use_box && e != hipErrorInvalidValue) {
+      return bad(e, "pyramid box level");
+    } else if (D > 0 && top_blocks > 0 && n_top <= ((int64_t)1 << 28)) {
+      // the whole top level in one launch (column layout), then descend
+      if ((e = nodes[D].ensure_exact((size_t)n_top * sizeof(uint64_t))) != hipSuccess ||
+          (e = vals[D].ensure_exact((size_t)n_top * sizeof(double))) != hipSuccess)
+        return bad(e, "pyramid top level");
+      if ((e = partials.ensure_exact((size_t)std::max<int64_t>(top_blocks, pyr_blocks(INT64_MAX / 2)) *
+                                 sizeof(PyrPartial))) != hipSuccess)
+        return bad(e, "pyramid partials");
+      if ((e = launch_pyr_top_bound(x.L, lev[D], D, (int32_t)nj, x.scans, x.angles, x.pts, x.n_used, x.step,
+                                    (uint64_t*)nodes[D].p, (double*)vals[D].p, (PyrPartial*)partials.p,
+                                    x.stream)) != hipSuccess)
+        return bad(e, "pyr_top_bound_kernel");
+      *top_scored = n_top;
+      if ((e = descend(D, n_top, n_top, true, top_blocks)) != hipSuccess) return bad(e, "pyramid level pass");
+    } else {
+      for (int64_t first = 0; first < n_top; first += capd[D]) {
+        const int64_t m = std::min(capd[D], n_top - first);
+        if ((e = launch_pyr_top(x.L, (int32_t)nj, first, m, (uint64_t*)nodes[D].p, x.stream)) != hipSuccess)
+          return bad(e, "pyr_top_kernel");
+        if ((e = level_pass(D, m, m, true)) != hipSuccess) return bad(e, "pyramid level pass");
+      }
     }
     return hipSuccess;
   }
@@ -356,75 +450,10 @@ hipError_t PyramidSearch::run(const PyrInputs& x, BestPartial* best, PyrStats* s
   };
   if (x.depth < 0 || x.depth > kPyrMaxDepth) return fail(hipErrorInvalidValue, "pyramid depth out of range");
   if ((e = I.build(x)) != hipSuccess) return fail(e, "pyramid levels");
-  const int64_t nj = ((int64_t)x.L.n_space + (1 << x.depth) - 1) >> x.depth;
-  const int64_t n_top = (int64_t)x.L.n_scans * x.L.n_angles * nj * nj;
-  I.set_caps(x.L, x.depth);
-  if ((e = I.ensure_lists(x.depth)) != hipSuccess) return fail(e, "pyramid node lists");
-  for (int d = 0; d <= kPyrMaxDepth; ++d) I.cslot[d] = 0;
-  I.next_slot = 1;
-  if ((e = launch_pyr_init(I.inc_dev(), I.scored_dev(), kPyrMaxDepth + 1 + Impl::kCountSlots, x.stream)) != hipSuccess)
-    return fail(e, "pyr_init_kernel");
-  int32_t ktiles, kt, col_blocks;
-  const int top_blocks = pyr_top_blocks(x.L, (int32_t)nj, &ktiles, &kt, &col_blocks);
-  const int D = x.depth;
   int64_t top_scored = 0;
-  // the top level as beam boxes: one-cell steps are given; the box test
-  // needs |t| < 2^24 (box_ok), nj <= 32, a launch of n_scans * n_angles waves
-  const int npc = pyr_topbox_pieces((int32_t)nj);
-  const int64_t box_blocks = (int64_t)x.L.n_scans * x.L.n_angles;
-  const bool use_box = x.top_mode == 0 && Impl::box_eligible(x, nj, n_top);
-  if (use_box && (e = I.build_box(x, D, (int32_t)nj, npc)) == hipSuccess) {
-    // the split waves' partial sums: only launches of few (window, angle)s split
-    const size_t slab_ints = Impl::box_slab_ints(x, n_top);
-    if ((e = I.top_sums.ensure_exact((size_t)n_top * sizeof(int32_t))) != hipSuccess ||
-        (e = I.top_thr.ensure_exact(2 * sizeof(int64_t))) != hipSuccess ||
-        (slab_ints && (e = I.top_slab.ensure_exact(slab_ints * sizeof(int32_t))) != hipSuccess))
-      return fail(e, "pyramid top level");
-    if ((e = I.partials.ensure_exact((size_t)std::max<int64_t>(box_blocks, pyr_blocks(INT64_MAX / 2)) *
-                               sizeof(PyrPartial))) != hipSuccess)
-      return fail(e, "pyramid partials");
-    if (x.timed && (e = I.mark_top(0, x.stream)) != hipSuccess) return fail(e, "hipEventRecord");
-    if ((e = launch_pyr_topbox(x.L, I.boxg, D, (int32_t)nj, x.scans, x.angles, x.pts, x.n_used, x.step,
-                               (int32_t*)I.top_sums.p, slab_ints ? (int32_t*)I.top_slab.p : nullptr,
-                               (PyrPartial*)I.partials.p, x.stream)) != hipSuccess)
-      return fail(e, "pyr_topbox_kernel");
-    if (x.timed) {
-      if ((e = I.mark_top(1, x.stream)) != hipSuccess) return fail(e, "hipEventRecord");
-      std::snprintf(I.st->top_name, sizeof(I.st->top_name), "pyr_topbox_kernel<%d,%d>", npc,
-                    (int)((nj * npc + 63) / 64));
-      I.st->top_bytes = (double)n_top * (double)x.n_used * 2.0;
-    }
-    top_scored = n_top;
-    I.st->top_box = 1;
-    I.top_implicit = D;
-    I.top_nj = (int32_t)nj;
-    e = I.descend(D, n_top, n_top, true, box_blocks);
-    I.top_implicit = -1;
-    if (e != hipSuccess) return fail(e, "pyramid level pass");
-  } else if (use_box && e != hipErrorInvalidValue) {
-    return fail(e, "pyramid box level");
-  } else if (D > 0 && top_blocks > 0 && n_top <= ((int64_t)1 << 28)) {
-    // the whole top level in one launch (column layout), then descend
-    if ((e = I.nodes[D].ensure_exact((size_t)n_top * sizeof(uint64_t))) != hipSuccess ||
-        (e = I.vals[D].ensure_exact((size_t)n_top * sizeof(double))) != hipSuccess)
-      return fail(e, "pyramid top level");
-    if ((e = I.partials.ensure_exact((size_t)std::max<int64_t>(top_blocks, pyr_blocks(INT64_MAX / 2)) *
-                               sizeof(PyrPartial))) != hipSuccess)
-      return fail(e, "pyramid partials");
-    if ((e = launch_pyr_top_bound(x.L, I.lev[D], D, (int32_t)nj, x.scans, x.angles, x.pts, x.n_used, x.step,
-                                  (uint64_t*)I.nodes[D].p, (double*)I.vals[D].p, (PyrPartial*)I.partials.p,
-                                  x.stream)) != hipSuccess)
-      return fail(e, "pyr_top_bound_kernel");
-    top_scored = n_top;
-    if ((e = I.descend(D, n_top, n_top, true, top_blocks)) != hipSuccess) return fail(e, "pyramid level pass");
-  } else {
-    for (int64_t first = 0; first < n_top; first += I.capd[D]) {
-      const int64_t m = std::min(I.capd[D], n_top - first);
-      if ((e = launch_pyr_top(x.L, (int32_t)nj, first, m, (uint64_t*)I.nodes[D].p, x.stream)) != hipSuccess)
-        return fail(e, "pyr_top_kernel");
-      if ((e = I.level_pass(D, m, m, true)) != hipSuccess) return fail(e, "pyramid level pass");
-    }
-  }
+  const char* msg = nullptr;
+  if ((e = I.search_levels(x, -DBL_MAX, &top_scored, &msg)) != hipSuccess) return fail(e, msg);
+  const int D = x.depth;
   // the incumbent and the scored counts, one copy
   if ((e = hipMemcpyAsync(I.h_inc(), I.state.p, sizeof(BestPartial) + (kPyrMaxDepth + 1) * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost, x.stream)) != hipSuccess)
@@ -448,6 +477,58 @@ hipError_t PyramidSearch::run(const PyrInputs& x, BestPartial* best, PyrStats* s
   }
   I.n_ev_bound = 0;
   I.st->nodes[D] += top_scored;
+  return hipSuccess;
+}
+
+hipError_t PyramidSearch::collect(const PyrInputs& x0, double T, int64_t capacity, PyrHit* hits, int64_t* n_found,
+                                  PyrStats* stats, std::string* what) {
+  Impl& I = *p_;
+  auto fail = [&](hipError_t err, const char* msg) {
+    I.collecting = false;
+    I.st = nullptr;
+    if (what) *what = msg;
+    return err;
+  };
+  if (x0.depth < 0 || x0.depth > kPyrMaxDepth || x0.L.n_scans != 1 || capacity < 1 || !hits || !n_found || !(T == T))
+    return fail(hipErrorInvalidValue, "collect: one window, a capacity and a threshold");
+  // the levels run built for this grid: nothing is built here
+  if (I.key_g != x0.level0.g || I.key_gen != x0.grid_gen || I.key_sx != x0.level0.width ||
+      I.key_sy != x0.level0.height || I.key_grids != x0.n_grids || I.built < x0.depth)
+    return fail(hipErrorInvalidValue, "collect: the pooled levels of this grid are not built (run first)");
+  PyrInputs x = x0;
+  x.timed = 0;
+  PyrStats local;
+  I.st = &local;
+  I.in = x;
+  I.lev[0] = x.level0;
+  I.collecting = true;
+  I.collect_T = T;
+  I.hit_cap = capacity;
+  hipError_t e;
+  if ((e = I.hits.ensure_exact((size_t)capacity * sizeof(PyrHit))) != hipSuccess ||
+      (e = I.h_hits.ensure_exact((size_t)capacity * sizeof(PyrHit))) != hipSuccess)
+    return fail(e, "collect list");
+  int64_t top_scored = 0;
+  const char* msg = nullptr;
+  if ((e = I.search_levels(x, T, &top_scored, &msg)) != hipSuccess) return fail(e, msg);
+  // the count, the scored counts and the list's first `capacity` slots, one wait
+  if ((e = hipMemcpyAsync(I.h_counts(), I.hits_dev(), sizeof(unsigned long long), hipMemcpyDeviceToHost, x.stream)) !=
+          hipSuccess ||
+      (e = hipMemcpyAsync(I.h_scored(), I.scored_dev(), (kPyrMaxDepth + 1) * sizeof(unsigned long long),
+                          hipMemcpyDeviceToHost, x.stream)) != hipSuccess ||
+      (e = hipMemcpyAsync(I.h_hits.p, I.hits.p, (size_t)capacity * sizeof(PyrHit), hipMemcpyDeviceToHost, x.stream)) !=
+          hipSuccess ||
+      (e = hipStreamSynchronize(x.stream)) != hipSuccess)
+    return fail(e, "collect copy");
+  const int64_t n = (int64_t)I.h_counts()[0];
+  *n_found = n;
+  std::memcpy(hits, I.h_hits.p, (size_t)std::min(n, capacity) * sizeof(PyrHit));
+  if (stats) {
+    for (int d = 0; d <= kPyrMaxDepth; ++d) stats->collect_nodes[d] = (int64_t)I.h_scored()[d];
+    stats->collect_nodes[x.depth] += top_scored;
+  }
+  I.collecting = false;
+  I.st = nullptr;
   return hipSuccess;
 }
 

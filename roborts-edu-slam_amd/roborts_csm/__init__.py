@@ -630,6 +630,60 @@ class Context:
                                            _i64ptr(out) if kernel == 0 else None, n))
         return out
 
+    def search_match(self, points_cells, param, grid_index, centers_map, cov, max_depth: int = -1,
+                     probe_min_nodes: int = 0, node_capacity: int = 0, top_kernel: int = 0,
+                     collect_capacity: int = 0, min_response: float = 0.0) -> dict:
+        """csm_search_match: the reference's full ScanMatch result (response,
+        FindBestCandidate's averaged pose, covariances) for the best of many
+        windows, from the admissible search and a collect of the candidates
+        at or above the covariance bound. cov (float64, 9) is in/out. Returns
+        a dict: response, pose_map (map cells / rad), accepted, window, front
+        (CsmBest), count, path (_abi.MATCH_*), threshold, collected, search
+        (phase 1's stats), collect_nodes."""
+        pts = np.ascontiguousarray(points_cells, dtype=np.float64).reshape(-1, 2)
+        p = _as_param(param)
+        gi = np.ascontiguousarray(grid_index, dtype=np.int32)
+        ctr = np.ascontiguousarray(centers_map, dtype=np.float64).reshape(-1, 3)
+        assert gi.size == ctr.shape[0]
+        assert cov.dtype == np.float64 and cov.flags.c_contiguous and cov.size == 9
+        opt = _abi.CsmMatchOptions(_abi.CsmSearchOptions(int(max_depth), int(probe_min_nodes), int(node_capacity),
+                                                         int(top_kernel), 0), int(collect_capacity), float(min_response))
+        r = _abi.CsmMatchResult()
+        self._check(_lib.csm_search_match(self._h, _dptr(pts), pts.shape[0], C.byref(p), gi.size,
+                                          gi.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(ctr), C.byref(opt),
+                                          _dptr(cov), C.byref(r)))
+        return match_result_dict(r)
+
+    def search_collect(self, points_cells, param, grid_index: int, center_map, depth: int, threshold: float,
+                       capacity: int | None = None):
+        """csm_search_collect (a test hook): every candidate of one window with
+        score >= threshold -> (flat int64, score float64, n_found), ascending
+        flat order; at most `capacity` (default: every candidate) are
+        returned, n_found counts them all."""
+        pts = np.ascontiguousarray(points_cells, dtype=np.float64).reshape(-1, 2)
+        p = _as_param(param)
+        ctr = np.ascontiguousarray(center_map, dtype=np.float64).reshape(3)
+        na, ns = window_dims(p)
+        cap = na * ns * ns if capacity is None else int(capacity)
+        flat = np.full(max(cap, 1), -1, dtype=np.int64)
+        score = np.full(max(cap, 1), np.nan)
+        n = C.c_int64(-1)
+        self._check(_lib.csm_search_collect(self._h, _dptr(pts), pts.shape[0], C.byref(p), int(grid_index), _dptr(ctr),
+                                            int(depth), float(threshold), _i64ptr(flat), _dptr(score), cap,
+                                            C.byref(n)))
+        return flat[:cap], score[:cap], int(n.value)
+
+
+def match_result_dict(r) -> dict:
+    """A csm_match_result as a dict (Context.search_match, LoopClosure.match_full)."""
+    st = r.search
+    return dict(response=r.response, pose_map=np.array(list(r.pose_map)), accepted=bool(r.accepted),
+                window=int(r.window), front=r.front, count=int(r.count), path=int(r.path), threshold=r.threshold,
+                collected=int(r.collected), collect_nodes=list(r.collect_nodes),
+                search=dict(depth=st.depth, exhaustive=bool(st.exhaustive), candidates=st.candidates,
+                            nodes=list(st.nodes), probe_leaves=st.probe_leaves, beam_reads=st.beam_reads,
+                            build_ms=st.build_ms, syncs=st.syncs, top_box=bool(st.top_box)))
+
 
 class _PinnedBlock:
     """One csm_host_alloc allocation, freed when the last array over it dies."""

@@ -37,6 +37,7 @@ EXPORTED = (
     "csm_set_grid_stack", "csm_best_windows", "csm_optimize_scan_match", "csm_optimize_scan_match_batch",
     "csm_optimize_update_cost", "csm_load_scans_grids", "csm_scan_matchers_batch_grids",
     "csm_search_windows", "csm_search_bounds", "csm_host_plan_compute", "csm_get_host_plan",
+    "csm_search_match", "csm_search_collect",
     # include/csm_gridmap.h
     "csm_gridmap_create", "csm_gridmap_destroy", "csm_gridmap_last_error",
     "csm_gridmap_set_options", "csm_gridmap_set_cell_params", "csm_gridmap_set_map_offset",
@@ -49,7 +50,7 @@ EXPORTED = (
     "csm_frontend_last_phases", "csm_frontend_process_ranges",
     # include/csm_loop_closure.h
     "csm_loop_closure_create", "csm_loop_closure_destroy", "csm_loop_closure_last_error",
-    "csm_loop_closure_set_submaps", "csm_loop_closure_match",
+    "csm_loop_closure_set_submaps", "csm_loop_closure_match", "csm_loop_closure_match_full",
     # include/csm_backend.h
     "csm_backend_create", "csm_backend_destroy", "csm_backend_last_error", "csm_backend_add_scan",
     "csm_backend_set_scan_pose", "csm_backend_scan_match", "csm_backend_map",
@@ -133,6 +134,37 @@ class CsmSearchStats(C.Structure):
         ("syncs", C.c_int64),
         ("top_box", C.c_int32),
         ("reserved", C.c_int32),
+    ]
+
+
+class CsmMatchOptions(C.Structure):
+    """csm_match_options (include/csm.h): csm_search_match."""
+    _fields_ = [
+        ("search", CsmSearchOptions),
+        ("collect_capacity", C.c_int64),
+        ("min_response", C.c_double),
+    ]
+
+
+# enum csm_match_path
+MATCH_PRUNED, MATCH_TIE, MATCH_OVERFLOW, MATCH_UNPOOLED, MATCH_LOW_RESPONSE, MATCH_NO_RESPONSE = range(6)
+
+
+class CsmMatchResult(C.Structure):
+    """csm_match_result (include/csm.h): the full ScanMatch result of the
+    admissible search's winner window."""
+    _fields_ = [
+        ("response", C.c_double),
+        ("pose_map", C.c_double * 3),
+        ("accepted", C.c_int32),
+        ("window", C.c_int32),
+        ("front", CsmBest),
+        ("count", C.c_int32),
+        ("path", C.c_int32),
+        ("threshold", C.c_double),
+        ("collected", C.c_int64),
+        ("search", CsmSearchStats),
+        ("collect_nodes", C.c_int64 * 11),
     ]
 
 
@@ -279,6 +311,10 @@ def _bind(lib: C.CDLL) -> C.CDLL:
                                          C.POINTER(CsmSearchStats)]),
         "csm_search_bounds": (C.c_int, [_ctx, _dp, C.c_int32, C.POINTER(CsmParam), C.c_int32, _i32p, _dp,
                                         C.c_int32, C.c_int32, _dp, _i64p, C.c_int64]),
+        "csm_search_match": (C.c_int, [_ctx, _dp, C.c_int32, C.POINTER(CsmParam), C.c_int32, _i32p, _dp,
+                                       C.POINTER(CsmMatchOptions), _dp, C.POINTER(CsmMatchResult)]),
+        "csm_search_collect": (C.c_int, [_ctx, _dp, C.c_int32, C.POINTER(CsmParam), C.c_int32, _dp, C.c_int32,
+                                         C.c_double, _i64p, _dp, C.c_int64, _i64p]),
         "csm_host_plan_compute": (C.c_int, [C.c_int32, C.c_int32, _i32p, C.c_int32, C.POINTER(CsmHostPlan)]),
         "csm_get_host_plan": (C.c_int, [_ctx, C.POINTER(CsmHostPlan)]),
         "csm_optimize_scan_match": (C.c_int, [_ctx, _dp, C.c_int32, C.POINTER(CsmOptimizeParam), _dp, _dp]),
@@ -325,6 +361,8 @@ def _bind(lib: C.CDLL) -> C.CDLL:
                                                    C.c_int64]),
         "csm_loop_closure_match": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.POINTER(CsmParam), _dp, C.c_int32,
                                              C.POINTER(CsmLoopClosureResult)]),
+        "csm_loop_closure_match_full": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.POINTER(CsmParam), _dp, C.c_int32, _dp,
+                                                  C.POINTER(CsmLoopClosureResult), C.POINTER(CsmMatchResult)]),
         "csm_backend_create": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
         "csm_backend_destroy": (C.c_int, [C.c_void_p]),
         "csm_backend_last_error": (C.c_char_p, [C.c_void_p]),

@@ -180,6 +180,29 @@ class DeviceLoopClosure:
         self.last_search_ms, self.last_exchange_ms = float(r.search_ms), float(r.exchange_ms)
         return LoopClosureResult(r.score, r.global_index, r.submap, r.x, r.y, r.angle)
 
+    def match_full(self, points_cells, param, pose_world, cov, search: str = "pyramid"):
+        """csm_loop_closure_match_full: match(), then the winning submap's full
+        ScanMatch result (csm_search_match on the device that holds it) ->
+        (LoopClosureResult, match dict as Context.search_match returns it).
+        cov (float64, 9) is in/out; last_pose_world is the averaged pose's
+        world coordinates."""
+        from . import _as_param, match_result_dict
+        from ._abi import CsmLoopClosureResult, CsmMatchResult
+        C = self._C
+        pts = np.ascontiguousarray(points_cells, dtype=np.float64).reshape(-1, 2)
+        pose = np.ascontiguousarray(pose_world, dtype=np.float64)
+        assert cov.dtype == np.float64 and cov.flags.c_contiguous and cov.size == 9
+        p = _as_param(param)
+        r, m = CsmLoopClosureResult(), CsmMatchResult()
+        dp = C.POINTER(C.c_double)
+        self._check(self._lib.csm_loop_closure_match_full(self._h, pts.ctypes.data_as(dp), pts.shape[0], C.byref(p),
+                                                          pose.ctypes.data_as(dp), 0 if search == "pyramid" else 1,
+                                                          cov.ctypes.data_as(dp), C.byref(r), C.byref(m)))
+        self.last_pose_world = np.array(r.pose_world[:])
+        self.last_n_devices = int(r.n_devices)
+        self.last_search_ms, self.last_exchange_ms = float(r.search_ms), float(r.exchange_ms)
+        return LoopClosureResult(r.score, r.global_index, r.submap, r.x, r.y, r.angle), match_result_dict(m)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.csm_loop_closure_destroy(self._h)
