@@ -605,11 +605,28 @@ int csm_search_bounds(csm_ctx* ctx, const double* points_xy, int32_t n_points,
  * reference does (:835-869). Where std::sort's order among equal scores could
  * change an output, or the set outgrows collect_capacity, the winner window is
  * scored exhaustively and finished as csm_scan_match finishes it: the result
- * is the reference's either way, never approximate. */
+ * is the reference's either way, never approximate.
+ *
+ * The collected list stays on the device. A set larger than the context's
+ * reduce minimum (CSM_LIST_REDUCE_MIN at csm_create, default 8192) is not
+ * copied and sorted whole: a device selection keeps what the finish reads --
+ * the 22 best scores and FindBest's band, and the 22 best of the candidates
+ * near the best pose, each closed under ties -- and the host finishes that
+ * subset (csrc/csm_search_match.hpp states why it is sufficient). A selection
+ * of more than 10240 (a huge band, or that many tied scores) falls back to
+ * the whole list: the same bits, only slower. */
+#define CSM_COLLECT_AUTO (-1)
 typedef struct csm_match_options {
   csm_search_options search;  /* phase 1 (and the collect's top depth, list capacity, top kernel) */
-  int64_t collect_capacity;   /* candidates the collected list holds (0: 10240, the exact finish's
-                                 window size); more candidates at or above T: path 2 */
+  int64_t collect_capacity;   /* candidates the collected list holds. > 0: that many; more
+                                 candidates at or above T: path 2. 0 (and any negative value but
+                                 CSM_COLLECT_AUTO): 10240, the exact finish's window size.
+                                 CSM_COLLECT_AUTO (-1): the list starts at the larger of 10240 and
+                                 what it grew to earlier on this context; when the count exceeds
+                                 it, the list grows to the count and the collect runs once more
+                                 (the grown list is kept, so steady-state calls descend once).
+                                 Path 2 only above min(n_cand, 2^26) entries (1 GiB), or when
+                                 that allocation fails. What loop-closure windows should pass */
   double min_response;        /* best < min_response: path 4, no phase 2 (TryCloseLoop rejects on
                                  the response first; a low best makes T low and the set large).
                                  0: never skip */
@@ -648,8 +665,13 @@ typedef struct csm_match_result {
  * FINE the positional, SUPER the angular one); untouched on path 4. Path 5 is
  * taken only when the response is not accepted (a negative threshold goes
  * through the collect). param->type == CSM_FAST: CSM_ERR_INVALID_ARG.
- * kernel_stats: "pyr_collect" (the collect's descent) and
- * "search_match:exhaustive" (launches = the count of fallbacks). */
+ * kernel_stats: "pyr_collect" (the collect's descent),
+ * "search_match:exhaustive" (launches = the count of fallbacks),
+ * "list_select" (the device selections' time and kernel launches),
+ * "search_match:reduced" (launches = calls finished from a selected subset),
+ * "search_match:reduce_overflow" (a selection outgrew 10240: the whole list
+ * was finished) and "search_match:regrown" (automatic capacity grew the list
+ * and collected again). */
 int csm_search_match(csm_ctx* ctx, const double* points_xy, int32_t n_points, const csm_param* param,
                      int32_t n_windows, const int32_t* grid_index, const double* centers_map,
                      const csm_match_options* options, double cov[9], csm_match_result* result);
@@ -664,6 +686,19 @@ int csm_search_match(csm_ctx* ctx, const double* points_xy, int32_t n_points, co
 int csm_search_collect(csm_ctx* ctx, const double* points_xy, int32_t n_points, const csm_param* param,
                        int32_t grid_index, const double center_map[3], int32_t depth, double threshold,
                        int64_t* flat, double* score, int64_t capacity, int64_t* n_found);
+
+/* Test hook: the device selection the reduced finish runs, over the list
+ * (score[i], flat[i]), i < n, uploaded as the collect would have left it:
+ *   S = { h : pred(h) and (key(h) >= key_K or (band_on and DoubleEqual(h.score, best, 1e-2))) }
+ * key: the order-preserving 64-bit image of score + 0.0; key_K: the k-th
+ * largest key among the hits passing pred (the lowest when fewer than k
+ * pass); pred: always (near_on = 0), or the angular list's test (:994-996) on
+ * the candidate (x, y) of flat in the window near = {x0, y0, step, n_space,
+ * bx, by, tol}. S comes back in ascending flat order; *n_out counts all of it,
+ * at most `capacity` are written. */
+int csm_list_select(csm_ctx* ctx, const double* score, const int64_t* flat, int64_t n, int32_t k,
+                    int32_t band_on, double best, int32_t near_on, const double* near_window,
+                    int64_t* out_flat, double* out_score, int64_t capacity, int64_t* n_out);
 
 #ifdef __cplusplus
 }

@@ -89,6 +89,10 @@ int csm_loop_closure_match(csm_loop_closure* lc, const double* points_xy, int32_
  * match->pose_map, FindBestCandidate's averaged pose
  * (correlate_scan_matcher.h:670-710), with the submap's offset. match->window
  * is the submap. cov: row-major 3x3 in/out, as csm_search_match writes it.
+ * The finish runs with collect_capacity = CSM_COLLECT_AUTO: a loop-closure
+ * window holds far more than 10240 candidates at or above the threshold, and
+ * the default capacity sent every such call through the exhaustive path 2.
+ * The outputs are the same bits either way; match->path and the time differ.
  * param->type == CSM_FAST: CSM_ERR_INVALID_ARG. */
 int csm_loop_closure_match_full(csm_loop_closure* lc, const double* points_xy, int32_t n_points,
                                 const csm_param* param, const double pose_world[3], int32_t search,

@@ -643,6 +643,12 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState, csmh::Scan
   }
   int pipeline_min = 512;    // fewest scans the 3-level driver splits into parts (CSM_PIPELINE)
   bool skip_dead_lists = true;  // live_lists (CSM_SKIP_DEAD_LISTS=0: every level fills both lists)
+  // csm_search_match: collected sets larger than this are finished from the
+  // device selection's subset (CSM_LIST_REDUCE_MIN). 8192: the smallest power
+  // of two at which the reduced finish measured no slower than the whole-list
+  // one (profiles/list_reduce/speed.md: 0.300 against 0.289 ms at 3,969
+  // candidates, 0.354 against 0.558 ms at 8,649)
+  int64_t list_reduce_min = 8192;
   int pipeline_parts = 2;    // parts in flight (CSM_PIPELINE_PARTS: 2..kMaxParts; 2 measured fastest)
   int first_windows = 128;   // level_begin_split: windows the first part's first launch takes (CSM_FIRST_WINDOWS; 0: one launch)
   // submitted batches (the device has the previous batch's work queued): a

@@ -477,7 +477,10 @@ int csm_loop_closure_match_full(csm_loop_closure* lc, const double* pts, int32_t
   const double tx = s * lc->offsets[2 * (size_t)res->submap], ty = s * lc->offsets[2 * (size_t)res->submap + 1];
   const double center[3] = {s * pose_world[0] + tx, s * pose_world[1] + ty, pose_world[2]};  // GetMapCoordsPose, as the match
   DeviceRestore restore;
-  st = csm_search_match(lc->ctx[(size_t)r], pts, n_points, param, 1, &local, center, nullptr, cov, match);
+  csm_match_options mo{};
+  mo.search.max_depth = -1;  // as null options: the search's own choice
+  mo.collect_capacity = CSM_COLLECT_AUTO;
+  st = csm_search_match(lc->ctx[(size_t)r], pts, n_points, param, 1, &local, center, &mo, cov, match);
   if (st != CSM_OK)
     return lc->fail(st, "device " + std::to_string(lc->devices[(size_t)r]) + ": " + csm_last_error(lc->ctx[(size_t)r]));
   match->window = res->submap;  // the winner among all submaps

@@ -20,6 +20,7 @@
 #include <string>
 
 #include "csm_internal.hpp"
+#include "csm_search_match.hpp"  // SelectSpec
 
 namespace csm {
 
@@ -213,6 +214,23 @@ class PyramidSearch {
   // (nullable): collect_nodes only.
   hipError_t collect(const PyrInputs& in, double T, int64_t capacity, PyrHit* hits, int64_t* n_found,
                      PyrStats* stats, std::string* what);
+  // collect, the hits left on the device: *n_found as collect's; the list
+  // holds the first min(*n_found, capacity) of them until the next search or
+  // collect. The list's buffer only grows (list_capacity: the entries it has
+  // room for now), so a caller that sizes `capacity` by it descends once.
+  hipError_t collect_device(const PyrInputs& in, double T, int64_t capacity, int64_t* n_found, PyrStats* stats,
+                            std::string* what);
+  int64_t list_capacity() const;
+  // The selection of csm_select.hpp over the device list (its count read on
+  // the device; n_upper >= it sizes the launches): out[0, min(*n_out, out_cap))
+  // in any order (host memory), *n_out the selection's full count. One wait.
+  // *launches (nullable): the kernels launched.
+  hipError_t select(const SelectSpec& spec, int64_t n_upper, PyrHit* out, int64_t out_cap, int64_t* n_out,
+                    int* launches, hipStream_t stream, std::string* what);
+  // The device list's first n entries (n <= what the collect left there).
+  hipError_t fetch(int64_t n, PyrHit* out, hipStream_t stream, std::string* what);
+  // Test hook (csm_list_select): hits[0, n) becomes the device list.
+  hipError_t load_list(const PyrHit* hits, int64_t n, hipStream_t stream, std::string* what);
   // Nodes per level list (0: 4M) and the smallest level that gets an
   // incumbent probe below the top (0: 4096).
   void configure(int64_t node_capacity, int probe_min_nodes);
@@ -223,6 +241,8 @@ class PyramidSearch {
  private:
   struct Impl;
   Impl* p_;
+  hipError_t collect_impl(const PyrInputs& in, double T, int64_t capacity, PyrHit* hits, int64_t* n_found,
+                          PyrStats* stats, std::string* what);
 };
 
 }  // namespace csm

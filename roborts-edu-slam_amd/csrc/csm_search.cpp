@@ -15,6 +15,7 @@
 // fixed whatever the pruning rate.
 #include "csm_pyramid.hpp"
 #include "csm_resources.hpp"
+#include "csm_select.hpp"
 
 #include <algorithm>
 #include <cfloat>
@@ -75,6 +76,10 @@ struct PyramidSearch::Impl {
   int64_t hit_cap = 0;
   DevBuf hits;
   csmh::HostBuf h_hits;
+  // the selection over the list (csm_select.hpp): its state, its output
+  // (count, then entries) and the pinned copy of that output
+  DevBuf sel_state, sel_out;
+  csmh::HostBuf h_sel;
   // the beam-box top level: integer sums of the implicit node list
   DevBuf top_sums, top_thr, top_slab;
   int top_implicit = -1;  // its depth while a search runs (-1: the top is a node list)
@@ -482,6 +487,21 @@ hipError_t PyramidSearch::run(const PyrInputs& x, BestPartial* best, PyrStats* s
 
 hipError_t PyramidSearch::collect(const PyrInputs& x0, double T, int64_t capacity, PyrHit* hits, int64_t* n_found,
                                   PyrStats* stats, std::string* what) {
+  if (!hits) {
+    if (what) *what = "collect: one window, a capacity and a threshold";
+    return hipErrorInvalidValue;
+  }
+  return collect_impl(x0, T, capacity, hits, n_found, stats, what);
+}
+
+hipError_t PyramidSearch::collect_device(const PyrInputs& x0, double T, int64_t capacity, int64_t* n_found,
+                                         PyrStats* stats, std::string* what) {
+  return collect_impl(x0, T, capacity, nullptr, n_found, stats, what);
+}
+
+// hits: the host copy of the list's first `capacity` slots (null: the list stays on the device)
+hipError_t PyramidSearch::collect_impl(const PyrInputs& x0, double T, int64_t capacity, PyrHit* hits, int64_t* n_found,
+                                       PyrStats* stats, std::string* what) {
   Impl& I = *p_;
   auto fail = [&](hipError_t err, const char* msg) {
     I.collecting = false;
@@ -489,7 +509,7 @@ hipError_t PyramidSearch::collect(const PyrInputs& x0, double T, int64_t capacit
     if (what) *what = msg;
     return err;
   };
-  if (x0.depth < 0 || x0.depth > kPyrMaxDepth || x0.L.n_scans != 1 || capacity < 1 || !hits || !n_found || !(T == T))
+  if (x0.depth < 0 || x0.depth > kPyrMaxDepth || x0.L.n_scans != 1 || capacity < 1 || !n_found || !(T == T))
     return fail(hipErrorInvalidValue, "collect: one window, a capacity and a threshold");
   // the levels run built for this grid: nothing is built here
   if (I.key_g != x0.level0.g || I.key_gen != x0.grid_gen || I.key_sx != x0.level0.width ||
@@ -506,29 +526,104 @@ hipError_t PyramidSearch::collect(const PyrInputs& x0, double T, int64_t capacit
   I.hit_cap = capacity;
   hipError_t e;
   if ((e = I.hits.ensure_exact((size_t)capacity * sizeof(PyrHit))) != hipSuccess ||
-      (e = I.h_hits.ensure_exact((size_t)capacity * sizeof(PyrHit))) != hipSuccess)
+      (hits && (e = I.h_hits.ensure_exact((size_t)capacity * sizeof(PyrHit))) != hipSuccess)) {
+    I.hit_cap = 0;
     return fail(e, "collect list");
+  }
   int64_t top_scored = 0;
   const char* msg = nullptr;
   if ((e = I.search_levels(x, T, &top_scored, &msg)) != hipSuccess) return fail(e, msg);
-  // the count, the scored counts and the list's first `capacity` slots, one wait
+  // the count, the scored counts and (for a host copy) the list's first `capacity` slots, one wait
   if ((e = hipMemcpyAsync(I.h_counts(), I.hits_dev(), sizeof(unsigned long long), hipMemcpyDeviceToHost, x.stream)) !=
           hipSuccess ||
       (e = hipMemcpyAsync(I.h_scored(), I.scored_dev(), (kPyrMaxDepth + 1) * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost, x.stream)) != hipSuccess ||
-      (e = hipMemcpyAsync(I.h_hits.p, I.hits.p, (size_t)capacity * sizeof(PyrHit), hipMemcpyDeviceToHost, x.stream)) !=
-          hipSuccess ||
+      (hits && (e = hipMemcpyAsync(I.h_hits.p, I.hits.p, (size_t)capacity * sizeof(PyrHit), hipMemcpyDeviceToHost,
+                                   x.stream)) != hipSuccess) ||
       (e = hipStreamSynchronize(x.stream)) != hipSuccess)
     return fail(e, "collect copy");
   const int64_t n = (int64_t)I.h_counts()[0];
   *n_found = n;
-  std::memcpy(hits, I.h_hits.p, (size_t)std::min(n, capacity) * sizeof(PyrHit));
+  if (hits) std::memcpy(hits, I.h_hits.p, (size_t)std::min(n, capacity) * sizeof(PyrHit));
   if (stats) {
     for (int d = 0; d <= kPyrMaxDepth; ++d) stats->collect_nodes[d] = (int64_t)I.h_scored()[d];
     stats->collect_nodes[x.depth] += top_scored;
   }
   I.collecting = false;
   I.st = nullptr;
+  return hipSuccess;
+}
+
+int64_t PyramidSearch::list_capacity() const { return (int64_t)(p_->hits.cap / sizeof(PyrHit)); }
+
+hipError_t PyramidSearch::select(const SelectSpec& spec, int64_t n_upper, PyrHit* out, int64_t out_cap, int64_t* n_out,
+                                 int* launches, hipStream_t stream, std::string* what) {
+  Impl& I = *p_;
+  auto fail = [&](hipError_t err, const char* msg) {
+    if (what) *what = msg;
+    return err;
+  };
+  if (!I.hits.p || !I.state.p || I.hit_cap < 1 || out_cap < 0 || (out_cap > 0 && !out) || !n_out || spec.k < 1)
+    return fail(hipErrorInvalidValue, "select: no device list, or no output");
+  hipError_t e;
+  const size_t bytes = select_out_bytes(out_cap);
+  if ((e = I.sel_state.ensure_exact(sizeof(SelectState))) != hipSuccess ||
+      (e = I.sel_out.ensure_exact(bytes)) != hipSuccess || (e = I.h_sel.ensure_exact(bytes)) != hipSuccess)
+    return fail(e, "select buffers");
+  if ((e = launch_list_select((const PyrHit*)I.hits.p, I.hits_dev(), I.hit_cap, std::max<int64_t>(n_upper, 1), spec,
+                              (SelectState*)I.sel_state.p, (SelectHead*)I.sel_out.p, out_cap, stream, launches)) !=
+      hipSuccess)
+    return fail(e, "list select kernels");
+  // the count and the compacted entries, one copy, one wait
+  if ((e = hipMemcpyAsync(I.h_sel.p, I.sel_out.p, bytes, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(stream)) != hipSuccess)
+    return fail(e, "select copy");
+  SelectHead* h = I.h_sel.as<SelectHead>();
+  *n_out = (int64_t)h->count;
+  if (out_cap > 0) std::memcpy(out, select_entries(h), (size_t)std::min(*n_out, out_cap) * sizeof(PyrHit));
+  return hipSuccess;
+}
+
+hipError_t PyramidSearch::fetch(int64_t n, PyrHit* out, hipStream_t stream, std::string* what) {
+  Impl& I = *p_;
+  auto fail = [&](hipError_t err, const char* msg) {
+    if (what) *what = msg;
+    return err;
+  };
+  if (n < 0 || n > I.hit_cap || !I.hits.p || (n > 0 && !out)) return fail(hipErrorInvalidValue, "fetch: beyond the device list");
+  if (n == 0) return hipSuccess;
+  hipError_t e;
+  if ((e = I.h_hits.ensure_exact((size_t)n * sizeof(PyrHit))) != hipSuccess) return fail(e, "collect list");
+  if ((e = hipMemcpyAsync(I.h_hits.p, I.hits.p, (size_t)n * sizeof(PyrHit), hipMemcpyDeviceToHost, stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(stream)) != hipSuccess)
+    return fail(e, "collect copy");
+  std::memcpy(out, I.h_hits.p, (size_t)n * sizeof(PyrHit));
+  return hipSuccess;
+}
+
+hipError_t PyramidSearch::load_list(const PyrHit* hits, int64_t n, hipStream_t stream, std::string* what) {
+  Impl& I = *p_;
+  auto fail = [&](hipError_t err, const char* msg) {
+    if (what) *what = msg;
+    return err;
+  };
+  if (n < 0 || (n > 0 && !hits)) return fail(hipErrorInvalidValue, "load_list: no hits");
+  const int64_t cap = std::max<int64_t>(n, 1);
+  hipError_t e;
+  if ((e = I.state.ensure_exact(sizeof(BestPartial) + Impl::kStateWords * sizeof(unsigned long long))) != hipSuccess ||
+      (e = I.hits.ensure_exact((size_t)cap * sizeof(PyrHit))) != hipSuccess ||
+      (e = I.h_hits.ensure_exact((size_t)cap * sizeof(PyrHit) + sizeof(unsigned long long))) != hipSuccess)
+    return fail(e, "collect list");
+  // pinned: the hits, then their count
+  std::memcpy(I.h_hits.p, hits, (size_t)n * sizeof(PyrHit));
+  unsigned long long* h_n = (unsigned long long*)((char*)I.h_hits.p + (size_t)cap * sizeof(PyrHit));
+  *h_n = (unsigned long long)n;
+  if ((n > 0 && (e = hipMemcpyAsync(I.hits.p, I.h_hits.p, (size_t)n * sizeof(PyrHit), hipMemcpyHostToDevice, stream)) !=
+                    hipSuccess) ||
+      (e = hipMemcpyAsync(I.hits_dev(), h_n, sizeof(unsigned long long), hipMemcpyHostToDevice, stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(stream)) != hipSuccess)
+    return fail(e, "load_list copy");
+  I.hit_cap = cap;
   return hipSuccess;
 }
 

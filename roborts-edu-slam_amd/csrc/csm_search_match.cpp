@@ -97,6 +97,20 @@ double finish_complete(const FinishOut& o, const FinishWindow& W, int skip_lists
   return best_score > 1.0 ? 1.0 : best_score;  // :861-863
 }
 
+void sorted_best_xy(const PyrHit* hits, int64_t n, const FinishWindow& W, double* bx, double* by) {
+  struct Scores {
+    const PyrHit* h;
+    double operator[](int i) const { return h[i].score; }
+  };
+  struct Indices {
+    const PyrHit* h;
+    int64_t operator[](int i) const { return h[i].flat; }
+  };
+  auto cos_sin = [&](int a) { return CosSin{W.angles[a].cosine, W.angles[a].sine}; };
+  FinishOut o{};
+  find_best(Scores{hits}, Indices{hits}, (int)n, hits[0].score, W.grid, cos_sin, &o, bx, by);
+}
+
 void list_finish(PyrHit* hits, int64_t n, const FinishWindow& W, double cov[9], ListFinish* out) {
   std::sort(hits, hits + n, [](const PyrHit& a, const PyrHit& b) { return a.score > b.score; });
   *out = ListFinish{};

@@ -639,7 +639,8 @@ class Context:
         at or above the covariance bound. cov (float64, 9) is in/out. Returns
         a dict: response, pose_map (map cells / rad), accepted, window, front
         (CsmBest), count, path (_abi.MATCH_*), threshold, collected, search
-        (phase 1's stats), collect_nodes."""
+        (phase 1's stats), collect_nodes. collect_capacity: 0 = 10240 entries,
+        -1 (COLLECT_AUTO) = a list that grows to the set's size."""
         pts = np.ascontiguousarray(points_cells, dtype=np.float64).reshape(-1, 2)
         p = _as_param(param)
         gi = np.ascontiguousarray(grid_index, dtype=np.int32)
@@ -672,6 +673,28 @@ class Context:
                                             int(depth), float(threshold), _i64ptr(flat), _dptr(score), cap,
                                             C.byref(n)))
         return flat[:cap], score[:cap], int(n.value)
+
+
+    def list_select(self, score, flat, k: int, band_on: bool = False, best: float = 0.0, near=None,
+                    capacity: int | None = None):
+        """csm_list_select (a test hook): the device selection the reduced
+        finish runs, over the list (score[i], flat[i]) -> (flat int64, score
+        float64, n_out) in ascending flat order. near: None, or (x0, y0, step,
+        n_space, bx, by, tol). At most `capacity` (default: the list's length)
+        entries come back, n_out counts the whole selection; slots past it
+        keep flat -1 / score NaN."""
+        sc = np.ascontiguousarray(score, dtype=np.float64).reshape(-1)
+        fl = np.ascontiguousarray(flat, dtype=np.int64).reshape(-1)
+        assert sc.size == fl.size
+        cap = sc.size if capacity is None else int(capacity)
+        out_flat = np.full(max(cap, 1), -1, dtype=np.int64)
+        out_score = np.full(max(cap, 1), np.nan)
+        nr = np.ascontiguousarray(near if near is not None else np.zeros(7), dtype=np.float64).reshape(7)
+        n = C.c_int64(-1)
+        self._check(_lib.csm_list_select(self._h, _dptr(sc), _i64ptr(fl), sc.size, int(k), int(bool(band_on)),
+                                         float(best), int(near is not None), _dptr(nr), _i64ptr(out_flat),
+                                         _dptr(out_score), cap, C.byref(n)))
+        return out_flat, out_score, int(n.value)
 
 
 def match_result_dict(r) -> dict:

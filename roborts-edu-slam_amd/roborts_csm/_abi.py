@@ -37,7 +37,7 @@ EXPORTED = (
     "csm_set_grid_stack", "csm_best_windows", "csm_optimize_scan_match", "csm_optimize_scan_match_batch",
     "csm_optimize_update_cost", "csm_load_scans_grids", "csm_scan_matchers_batch_grids",
     "csm_search_windows", "csm_search_bounds", "csm_host_plan_compute", "csm_get_host_plan",
-    "csm_search_match", "csm_search_collect",
+    "csm_search_match", "csm_search_collect", "csm_list_select",
     # include/csm_gridmap.h
     "csm_gridmap_create", "csm_gridmap_destroy", "csm_gridmap_last_error",
     "csm_gridmap_set_options", "csm_gridmap_set_cell_params", "csm_gridmap_set_map_offset",
@@ -315,6 +315,8 @@ def _bind(lib: C.CDLL) -> C.CDLL:
                                        C.POINTER(CsmMatchOptions), _dp, C.POINTER(CsmMatchResult)]),
         "csm_search_collect": (C.c_int, [_ctx, _dp, C.c_int32, C.POINTER(CsmParam), C.c_int32, _dp, C.c_int32,
                                          C.c_double, _i64p, _dp, C.c_int64, _i64p]),
+        "csm_list_select": (C.c_int, [_ctx, _dp, _i64p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_int32, _dp,
+                                      _i64p, _dp, C.c_int64, _i64p]),
         "csm_host_plan_compute": (C.c_int, [C.c_int32, C.c_int32, _i32p, C.c_int32, C.POINTER(CsmHostPlan)]),
         "csm_get_host_plan": (C.c_int, [_ctx, C.POINTER(CsmHostPlan)]),
         "csm_optimize_scan_match": (C.c_int, [_ctx, _dp, C.c_int32, C.POINTER(CsmOptimizeParam), _dp, _dp]),
