@@ -2,8 +2,9 @@
 // translation units: the context (csm_ctx), its buffers and worker pool, the
 // window plan, and the functions one unit calls in another.
 //
-//   csm_api.cpp          context lifetime, profiling, raw window kernels, the search
-//   csm_grid.cpp         resident grids: upload, refresh, stacks, borrowed maps
+//   csm_api.cpp          context lifetime, profiling, raw window kernels
+//   csm_search_entry.cpp the pooled search: csm_search_windows, csm_search_match, their hooks
+//   csm_grid.cpp        resident grids: upload, refresh, stacks, borrowed maps
 //   csm_launch.cpp       window plans and kernel launches (run_windows), joins
 //   csm_level.cpp        one level over a batch: planned, launched, joined, completed
 //   csm_pipeline.cpp     the pipelined 3-level driver, submitted batches in flight
@@ -144,6 +145,20 @@ struct CandGeom {
   double y(int64_t idx) const { return grid().y((int)idx); }
   const AngleEntry& a(int64_t idx) const { return angles[idx / nss]; }
 };
+
+// The csm_best of candidate `flat` of window W at step f cells; angles: the
+// call's whole table (W.angle_off indexes it).
+inline csm_best best_of(const Dims& D, const WindowPlan& W, const AngleEntry* angles, double f, double score,
+                        int64_t flat) {
+  const int64_t ns = D.n_space, nss = ns * ns;
+  csm_best b{};
+  b.score = score;
+  b.flat_index = flat;
+  b.x = W.x0 + (int)((flat / ns) % ns) * f;
+  b.y = W.y0 + (int)(flat % ns) * f;
+  b.angle = angles[(size_t)(W.angle_off + flat / nss)].angle;
+  return b;
+}
 
 // csm_host_finish.cpp
 void host_sort_finish(const double* scores, const Dims& D, const CandGeom& C, const csm_param& P,
@@ -709,6 +724,19 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState, csmh::Scan
     s.scorings = scorings;
     stats.push_back(s);
   }
+  // One timed span of `stream` between ev0 and ev1, in ms (profiling off: no
+  // calls, *ms untouched); a failure is hip_fail(e, what). run_windows records
+  // the same two events: end a span before anything that reaches it.
+  int span_begin(const char* what) {
+    const hipError_t e = profiling ? hipEventRecord(ev0, stream) : hipSuccess;
+    return e == hipSuccess ? CSM_OK : hip_fail(e, what);
+  }
+  int span_end(float* ms, const char* what) {
+    hipError_t e = hipSuccess;
+    if (profiling && (e = hipEventRecord(ev1, stream)) == hipSuccess && (e = hipEventSynchronize(ev1)) == hipSuccess)
+      e = hipEventElapsedTime(ms, ev0, ev1);
+    return e == hipSuccess ? CSM_OK : hip_fail(e, what);
+  }
 
   int fail(int code, const std::string& msg) {
     err = msg;
@@ -735,6 +763,30 @@ struct DeviceGuard {
     if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
   }
 };
+
+// csm_pipeline.cpp: a submitted batch still pending is completed (every entry
+// point but csm_scan_matchers_submit calls it first); the state's release
+int pipe_drain(csm_ctx* c);
+void pipe_free(csm_ctx* c);
+
+// An entry point that stages inputs in the context's pinned buffers, which
+// the next call rewrites (csm_search_entry.cpp): locked, on the context's
+// device, no batch pending; a stream that a failed call may have left copying
+// out of the staging is drained first, and body()'s failure marks it so
+// (ADVICE r02).
+template <class F>
+int staged_call(csm_ctx* c, F&& body) {
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  if (const int dst = pipe_drain(c)) return dst;  // a submitted batch still reads the context
+  if (c->staging_dirty) {
+    (void)hipStreamSynchronize(c->stream);
+    c->staging_dirty = false;
+  }
+  const int st = body();
+  c->staging_dirty = st != CSM_OK;
+  return st;
+}
 
 // Scores windows_n windows of one level on the device. plans[i] describes
 // window i, pts_dev is the batch's points already resident. When best_out is
@@ -828,10 +880,6 @@ constexpr double kOptMaxCost = 1.0 * kOptCostPointSize;   // :235
 
 inline bool map_ready(const csm_ctx* c) { return c->has_grid && c->info.update_index >= 0; }
 
-// csm_pipeline.cpp: a submitted batch still pending is completed (every entry
-// point but csm_scan_matchers_submit calls it first); the state's release
-int pipe_drain(csm_ctx* c);
-void pipe_free(csm_ctx* c);
 // csm_batch.cpp: no batch loaded, none pending, none queued (what a synchronous load starts from)
 int unload_batch(csm_ctx* c);
 int load_scans_locked(csm_ctx* c, int32_t n_scans, const double* pts, const int64_t* offsets);

@@ -40,7 +40,7 @@ struct FinishArgs {
   int64_t score_stride;  // scores between consecutive windows (0: n_cand)
   int32_t n_space;
   // Covariance lists nobody reads (bit 0: positional, bit 1: angular). In the
-  // 3-level driver a later level overwrites them (csm_api.cpp live_lists);
+  // 3-level driver a later level overwrites them (csm_level.cpp live_lists);
   // the finish then decides and fills only FindBest's prefix and the rest.
   int32_t skip_lists;
   double step_cells;   // res / map_resolution
@@ -267,7 +267,7 @@ constexpr size_t finish_lds_bytes(int64_t n) { return finish_layout(n).total; }
 // A.host_flag (the few-window path): the caller's scoring launch zeroed
 // exact_list[0] already; the exact pass then signals the host when done.
 // exact_on_device = false: only the fast pass runs; the windows it flags
-// (need_exact) are left for the host's std::sort (csm_api.cpp level_end).
+// (need_exact) are left for the host's std::sort (csm_level.cpp level_end).
 // The fast pass (when A.need_exact) and the exact pass on `stream`; with
 // exact_stream (and ev_fast, an event to record) the exact pass runs there,
 // after the fast pass.
@@ -433,7 +433,7 @@ hipError_t launch_score_box(const LevelWork& L, const ScanWork* d_scans, const d
                             hipStream_t stream);
 // Phase kernel (v7, csm_phase.hip): INT mode, sub-cell window step f < 1.
 // A beam's cell offset for candidate j is floor(phase + j*f), constant over
-// each phase bucket; the host builds the buckets (csm_api.cpp phase_table).
+// each phase bucket; the host builds the buckets (csm_launch.cpp phase_table).
 constexpr int kPhaseMaxBuckets = 8;
 constexpr int kPhaseMaxSpace = 16;
 struct PhaseTable {
