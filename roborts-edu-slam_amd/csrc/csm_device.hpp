@@ -1,4 +1,4 @@
-// csm_device.hpp — device helpers shared by the scoring kernels.
+// csm_device.hpp — device helpers shared by the scoring and finish kernels.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -81,6 +81,42 @@ __device__ __forceinline__ double bcast_lane(double v, int l) {
   const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)u, l);
   const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(u >> 32), l);
   return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+}
+
+// Wave (64 lanes) helpers.
+__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
+__device__ __forceinline__ int popc(uint64_t m) { return __popcll(m); }
+__device__ __forceinline__ uint64_t below_mask(int lane) {
+  return lane == 0 ? 0ull : (~0ull >> (64 - lane));
+}
+__device__ __forceinline__ uint64_t above_mask(int lane) {
+  return lane == 63 ? 0ull : (~0ull << (lane + 1));
+}
+__device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ int read_lane_i(int x, int l) { return __builtin_amdgcn_readlane(x, l); }
+__device__ __forceinline__ int wave_sum_i(int v) {
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// Host signal of a finish pass (A.host_flag): every block's FinishOut stores
+// complete, then the blocks count in on A.done_ctr; the last one resets the
+// counter and release-stores A.flag_value at system scope: at A.host_flag if
+// main() says so (asked then, after every block's count-in), and at `also`
+// if given. The count-in is relaxed (the ordering argument: DESIGN §7 "Host
+// signals").
+template <class Main>
+__device__ __forceinline__ void signal_host(const FinishArgs& A, Main main, int32_t* also) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const int t = __hip_atomic_fetch_add(A.done_ctr, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (t == (int)gridDim.x - 1) {
+      __hip_atomic_store(A.done_ctr, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (main()) __hip_atomic_store(A.host_flag, A.flag_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      if (also) __hip_atomic_store(also, A.flag_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
 }
 
 // Cross-lane sums without the LDS unit (ds_bpermute): DPP within a row of 16

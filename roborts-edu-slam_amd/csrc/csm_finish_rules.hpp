@@ -5,7 +5,7 @@
 // 607-611), FindBestCandidate's tied prefix and weighted sums (:670-710) and
 // the candidate lists of ComputePositionalCovariance / ComputeAngularCovariance
 // (:887-1003). Four finishes apply these rules: the fast pass
-// (finish_fast_body, csm_finish.hip), the fused fast pass (tail::finish,
+// (finish_fast_body, csm_finish_fast.hip), the fused fast pass (tail::finish,
 // csm_tail.hpp), the exact pass (finish_window, csm_finish.hip) and the host's
 // std::sort (host_sort_finish, csm_host_finish.cpp). The fast forms add "no
 // tie here can change an output, so no sort is needed".

@@ -31,7 +31,7 @@ struct AngleEntry {
   double angle, cosine, sine;
 };
 
-// ---- device finish (csm_finish.hip) -------------------------------------
+// ---- device finish (csm_finish.hip, csm_finish_fast.hip) ----------------
 constexpr int kCovPoints = 20;          // kMaxVarianceUsePointSize (:1033)
 constexpr int64_t kFinishMaxCand = 10240;  // windows above this finish on the host (LDS: 160 KB)
 
@@ -223,46 +223,88 @@ struct PyrHit {
 constexpr int kBlock = 256;      // 4 waves
 constexpr int kChunk = 1024;     // beams staged in LDS per pass (16 KB)
 
-constexpr int kFinishWaveScratch = 640;  // bytes of per-wave scratch
 #ifndef CSM_FINISH_WAVES
 #define CSM_FINISH_WAVES 4
 #endif
 constexpr int kFinishWaves = CSM_FINISH_WAVES;  // waves per window of the exact finish
-// misc block of the finish carve (csm_finish.hip Shared): counts, limits,
-// best (x, y), per-wave reductions
-constexpr size_t kFinishMisc = (48 + 16 * (size_t)kFinishWaves + 4 + 15) & ~(size_t)15;
+constexpr int kFinishDefer = 64;  // segments the partial sort may set aside
+
+// ---- LDS of the exact finish (finish_kernel, csm_finish.hip), stated once: the
+// structs the kernel lays over its dynamic LDS and the carve that places them.
+struct Seg {  // a segment [first, last) of the introsort loop and its remaining depth
+  int32_t first, last, depth;
+};
+struct WaveScratch {      // per-wave scratch of the register sort (csm_introsort.hpp sort_small)
+  uint8_t T[72], U[72];   // lane of the k-th right / left stop
+  Seg st[40];             // sub-segment stack
+  uint8_t pad[16];        // (the carve's 640 bytes a wave)
+};
+struct SortCounters {     // LevelSort's shared state (csm_introsort.hpp)
+  int32_t top, pending;   // segments in the current level's list / appended to the next one's
+  int32_t ndef;           // segments set aside (deferred list)
+  int32_t pad;            // a list overflowed ("cannot happen"): the window reports count = -1
+  int32_t trace;          // CSM_FINISH_TRACE builds: the window's trace row, -1: none
+};
+struct BlockPartition {   // partition_block's scratch
+  int32_t wl[kFinishWaves], wr[kFinishWaves];  // per-wave counts
+  int32_t fail;                                // first rank that is not a pair
+};
+struct FinishShared {     // misc block of the carve: counts, limits, best (x, y), per-wave reductions
+  SortCounters sort;
+  int32_t cnt_a, cnt_b, nan;
+  double bx, by;
+  double red[kFinishWaves];
+  BlockPartition part;
+};
 
 struct FinishLayout {
   size_t wave_scratch, defer, keys, vals, lpos, rpos, stack, fout, total;
+  int32_t seg_cap;  // segments each of the two per-level lists in `stack` holds
 };
-constexpr int kFinishDefer = 64;  // segments the partial sort may set aside (12 B each)
 
 // LDS carve of the finish kernel for n candidates (16-byte aligned pieces):
 // misc | kFinishWaves wave scratches | deferred segments | keys f64[n] | vals u16[n] |
 // lpos u16[n] | rpos u16[n] | shared segment stack | FinishOut.
+constexpr size_t finish_align16(size_t b) { return (b + 15) & ~(size_t)15; }
 constexpr FinishLayout finish_layout(int64_t n) {
   FinishLayout L{};
-  size_t o = kFinishMisc;
+  L.seg_cap = (int32_t)(n / 16 + 64) / 2;
+  size_t o = finish_align16(sizeof(FinishShared));
   L.wave_scratch = o;
-  o += (size_t)kFinishWaves * kFinishWaveScratch;
+  o += (size_t)kFinishWaves * sizeof(WaveScratch);
   L.defer = o;
-  o += (size_t)kFinishDefer * 12;
+  o += (size_t)kFinishDefer * sizeof(Seg);
   L.keys = o;
-  o += (size_t)n * 8;
+  o += (size_t)n * sizeof(double);
   L.vals = o;
-  o += ((size_t)n * 2 + 15) & ~(size_t)15;
+  o += finish_align16((size_t)n * sizeof(uint16_t));
   L.lpos = o;
-  o += ((size_t)n * 2 + 15) & ~(size_t)15;
+  o += finish_align16((size_t)n * sizeof(uint16_t));
   L.rpos = o;
-  o += ((size_t)n * 2 + 15) & ~(size_t)15;
+  o += finish_align16((size_t)n * sizeof(uint16_t));
   L.stack = o;
-  o += ((size_t)(n / 16 + 64) * 12 + 15) & ~(size_t)15;  // live segments
+  o += finish_align16((size_t)(n / 16 + 64) * sizeof(Seg));  // live segments: two lists
   L.fout = o;  // the window's FinishOut, assembled here and stored sealed
-  o += (sizeof(FinishOut) + 15) & ~(size_t)15;
+  o += finish_align16(sizeof(FinishOut));
   L.total = o;
   return L;
 }
 constexpr size_t finish_lds_bytes(int64_t n) { return finish_layout(n).total; }
+
+// The carve must not move (occupancy and the 160 KB limit depend on it): the
+// offsets the literal formula gave before the structs stated it.
+constexpr bool finish_layout_is(int64_t n, size_t vals, size_t lpos, size_t rpos, size_t stack, size_t fout,
+                                size_t total, int32_t seg_cap) {
+  const FinishLayout L = finish_layout(n);
+  return L.wave_scratch == 128 && L.defer == 2688 && L.keys == 3456 && L.vals == vals && L.lpos == lpos &&
+         L.rpos == rpos && L.stack == stack && L.fout == fout && L.total == total && L.seg_cap == seg_cap;
+}
+static_assert(kFinishWaves != 4 || (finish_layout_is(1, 3464, 3480, 3496, 3512, 4280, 4840, 32) &&
+                                    finish_layout_is(189, 4968, 5352, 5736, 6120, 7032, 7592, 37) &&
+                                    finish_layout_is(1331, 14104, 16776, 19448, 22120, 23896, 24456, 73) &&
+                                    finish_layout_is(6590, 56176, 69360, 82544, 95728, 101440, 102000, 237) &&
+                                    finish_layout_is(10240, 85376, 105856, 126336, 146816, 155264, 155824, 352)),
+              "the finish carve moved");
 
 // A.host_flag (the few-window path): the caller's scoring launch zeroed
 // exact_list[0] already; the exact pass then signals the host when done.
@@ -277,6 +319,10 @@ hipError_t launch_finish(const FinishArgs& A, const ScanWork* d_scans, const Ang
                          const double* d_scores, FinishOut* d_out, int32_t n_windows,
                          hipStream_t stream, hipStream_t exact_stream = nullptr, hipEvent_t ev_fast = nullptr,
                          bool fast_done = false);
+// The fast pass alone (csm_finish_fast.hip): one block per window, which settles
+// it or flags it (need_exact, exact_list) for the exact pass.
+hipError_t launch_fast(const FinishArgs& A, const ScanWork* d_scans, const AngleEntry* d_angles,
+                       const double* d_scores, FinishOut* d_out, int32_t n_windows, hipStream_t stream);
 
 // Launchers (csm_kernels.hip). All enqueue on `stream` and return hipError_t.
 // Column kernel (v2): lane = one (theta, x) column of a window, KT rows (y)

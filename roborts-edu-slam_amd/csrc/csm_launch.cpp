@@ -887,7 +887,7 @@ int Launch::finish_device() {
   hipError_t e;
   csm::FinishArgs A = finish_args(P, D, G, skip_lists);
   const size_t fbytes = (size_t)nw * sizeof(csm::FinishOut);
-  // + one "needs the exact sort" flag per window (fast finish, csm_finish.hip)
+  // + one "needs the exact sort" flag per window (fast finish, csm_finish_fast.hip)
   // + the flags' compacted list (count, then windows)
   const size_t lbytes = ((size_t)nw * sizeof(int32_t) + 7) & ~(size_t)7;  // the list's {count, tag}: 8-aligned
   if ((e = c->fin.ensure(fbytes + lbytes + (size_t)(nw + 2) * sizeof(int32_t))) != hipSuccess)

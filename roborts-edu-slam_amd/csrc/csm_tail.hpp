@@ -1,6 +1,6 @@
 // csm_tail.hpp — the fast finish fused into the scoring launch (r05).
 //
-// The separate fast finish (finish_fast_kernel, csm_finish.hip) was one more
+// The separate fast finish (finish_fast_kernel, csm_finish_fast.hip) was one more
 // dependent launch after every scoring launch of the 3-level driver: six per
 // config-2 step, ~40 us each, most of it the launch's ramp and the latency of
 // its one round of blocks. Here the scoring launch finishes each window

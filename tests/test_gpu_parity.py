@@ -14,6 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import pyoracle as O  # noqa: E402
+from sort_path_cases import killer as _killer  # noqa: E402
 
 
 def _param(a):
@@ -512,16 +513,6 @@ def test_fixed_point_path_out_of_grid(ctx):
                 sc = ctx.score_window(pts, p, np.array(center))
                 assert np.array_equal(sc, O.score_window(m, pts, p, np.array(center), sc.size))
     ctx.set_outside_value(0.3)
-
-
-def _killer(n):
-    """Median-of-3 killer-ish sequences that drive introsort to its depth limit."""
-    k = np.zeros(n)
-    half = n // 2
-    for i in range(half):
-        k[2 * i] = i + 1
-        k[2 * i + 1] = half + i + 1
-    return k[::-1].copy()
 
 
 @pytest.mark.parametrize("seed", [0, 1])

@@ -10,6 +10,7 @@ import pytest
 import pyoracle as O
 import wave_sort_model as W
 from introsort_ref import sort_order_greater
+from sort_path_cases import FAMILIES, SIZES
 
 
 def _cases(seed, n_cases):
@@ -30,6 +31,18 @@ def _cases(seed, n_cases):
 def test_device_formulation_matches_libstdcxx(seed):
     for k in _cases(seed, 60):
         assert np.array_equal(O.std_sort_order(k), np.array(W.device_sort_order(k)))
+
+
+@pytest.mark.parametrize("family", sorted(FAMILIES))
+def test_sizes_where_the_sort_changes_path(family):
+    """Both models against libstdc++ at the leaf threshold (16/17), the
+    register sort's limit (64/65), the block partition's (256/257) and around
+    them, for every key family."""
+    for n in SIZES:
+        k = FAMILIES[family](n)
+        ref = O.std_sort_order(k)
+        assert np.array_equal(ref, np.array(W.device_sort_order(k))), n
+        assert np.array_equal(ref, np.array(sort_order_greater(k))), n
 
 
 def test_all_equal_and_two_values():

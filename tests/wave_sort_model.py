@@ -1,5 +1,5 @@
 """Python model of the device finish's parallel std::sort emulation
-(roborts-edu-slam_amd/csrc/csm_finish.hip): explicit segment stack, median-of-3
+(roborts-edu-slam_amd/csrc/csm_introsort.hpp): explicit segment stack, median-of-3
 by one lane, the unguarded partition computed from rank-paired stop lists,
 heap sort at depth 0, then a stable insertion sort of every segment.
 Checked against libstdc++ (oracle) and tests/introsort_ref.py."""
