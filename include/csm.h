@@ -196,7 +196,10 @@ int csm_scan_match(csm_ctx* ctx, const double* points_xy, int32_t n_points,
                    double* response, int64_t* argmax_flat);
 
 /* ScanMatchers::ScanMatch with use_optimize_scan_match = false (both reference
- * YAMLs) and the grid already sized by the caller's MapSizeCheck:
+ * YAMLs; with it on, csm_optimize_scan_match_batch_grids followed by
+ * csm_scan_matchers_batch_grids_seeded is the same call for a batch, as
+ * csm_backend.h composes them) and the grid already sized by the caller's
+ * MapSizeCheck:
  * levels[0..2] = coarse, fine, super-fine params, all matched on the current
  * grid (scan_matchers.h:238,249,256). use_fine = false runs only the coarse
  * level. score = mean of the level responses (:281). */
@@ -444,6 +447,19 @@ int csm_optimize_scan_match(csm_ctx* ctx, const double* points_xy, int32_t n_poi
 int csm_optimize_scan_match_batch(csm_ctx* ctx, int32_t n_scans, const double* points_xy,
                                   const int64_t* point_offsets, const csm_optimize_param* param,
                                   double* poses, double* costs, int32_t* iterations);
+/* csm_optimize_scan_match_batch with scan i on grid grid_index[i] of the resident
+ * stack (NULL: grid 0), the whole solve in one launch: one workgroup per scan
+ * iterates on the device (glibc's sincos restated as in csm_sincos_device, the
+ * LDLT solve and the step in one lane), normalize_angle and the world pose on
+ * the host after the single synchronize. Same bits as the host-loop form:
+ * with CSM_DEVICE_TRIG=0 or a libm that did not pass the table checks the call
+ * is the host loop's, and a scan whose angle leaves the restated sincos'
+ * domain is run again by the host loop (csm_kernel_stats counts both, as
+ * optimize:host_batches and optimize:host_scans). */
+int csm_optimize_scan_match_batch_grids(csm_ctx* ctx, int32_t n_scans, const double* points_xy,
+                                        const int64_t* point_offsets, const int32_t* grid_index,
+                                        const csm_optimize_param* param, double* poses, double* costs,
+                                        int32_t* iterations);
 
 /* Test hook: one UpdateCost evaluation (optimize_scan_matcher.h:154-221) on
  * the device at a map-cell pose; cost normalised as the reference (:220), H
@@ -462,6 +478,15 @@ int csm_scan_matchers_batch_grids(csm_ctx* ctx, int32_t n_scans, const double* p
                                   const int64_t* point_offsets, const int32_t* grid_index,
                                   const csm_param levels[3], int32_t use_fine, double* poses,
                                   double* covs, double* scores);
+/* csm_scan_matchers_batch_grids from ScanMatchers::ScanMatch's state after its
+ * Gauss-Newton step (scan_matchers.h:205-281): runs levels[first_level ..] (first_level 0 or 1;
+ * 1 needs use_fine), score_seed (nullable) starts each scan's running sum and counts as one
+ * term of the mean: score = (seed + sum of responses) / (levels run + (seed ? 1 : 0)). */
+int csm_scan_matchers_batch_grids_seeded(csm_ctx* ctx, int32_t n_scans, const double* points_xy,
+                                         const int64_t* point_offsets, const int32_t* grid_index,
+                                         const csm_param levels[3], int32_t first_level, int32_t use_fine,
+                                         const double* score_seed, double* poses, double* covs,
+                                         double* scores);
 
 /* --- measurement ---------------------------------------------------------- */
 /* HIP-event timing of scoring launches (resets the stats): 0 off, 1 every

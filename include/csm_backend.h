@@ -22,9 +22,17 @@
  * reference's call on its single pair of back-end maps, and a J-job call
  * equals J such calls as long as no MapSizeCheck grows a map (then that pair
  * keeps its growth, as the reference's pair would). When every job's fine map
- * has the same geometry and the Gauss-Newton matcher is off (both reference
- * YAMLs), the correlative levels of all jobs run as one batch over a stack of
- * the fine maps (csm_scan_matchers_batch_grids).
+ * has the same geometry and every job the same use_fine_scan_match, the
+ * correlative levels of all jobs run as one batch over a stack of the fine
+ * maps (csm_scan_matchers_batch_grids). With the Gauss-Newton matcher on
+ * (ParamConfig's default) and the coarse maps of one geometry too, it runs
+ * first for all jobs in one launch over a stack of the coarse maps
+ * (csm_optimize_scan_match_batch_grids), and the jobs then split by the
+ * reference's test (scan_matchers.h:224): those it failed on, or all without
+ * use_fine_scan_match, run every level from their original pose; the others
+ * run the fine and super-fine levels from the Gauss-Newton pose with its
+ * score as one term of the mean (csm_scan_matchers_batch_grids_seeded). Any
+ * other call runs job by job.
  *
  * Kept scans mirror SensorDataManager (slam/sensor_data_manager.h:366-592):
  * csm_backend_add_scan keeps the endpoints in metres with their sensor pose
@@ -94,6 +102,10 @@ int csm_backend_scan_match(csm_backend* be, csm_gridmap* pub_map, const double c
                            csm_backend_job* jobs, int32_t n_jobs);
 /* Borrow map pair `slot` (which: 0 coarse, 1 fine); null before first use. */
 int csm_backend_map(csm_backend* be, int32_t slot, int32_t which, csm_gridmap** map);
+/* Borrow a matcher context of the batched path (which: 0 the fine stack's, 1
+ * the coarse one's; null when the service has none), e.g. for
+ * csm_set_profiling / csm_kernel_stats around a csm_backend_scan_match. */
+int csm_backend_matcher(csm_backend* be, int32_t which, csm_ctx** ctx);
 
 #ifdef __cplusplus
 }

@@ -41,7 +41,7 @@ struct csm_backend {
   csm_backend_param p{};
   std::string err;
   csm_ctx* ctx = nullptr;         // correlative levels, one job at a time
-  csm_ctx* ctx_coarse = nullptr;  // Gauss-Newton on a coarse map
+  csm_ctx* ctx_coarse = nullptr;  // Gauss-Newton on a coarse map, or of all jobs over a stack of coarse maps
   csm_ctx* ctx_stack = nullptr;   // correlative levels of all jobs over a stack of fine maps
   std::vector<KeptScan> scans;
   std::vector<MapPair> pairs;
@@ -164,6 +164,12 @@ int csm_backend_map(csm_backend* b, int32_t slot, int32_t which, csm_gridmap** m
   return CSM_OK;
 }
 
+int csm_backend_matcher(csm_backend* b, int32_t which, csm_ctx** ctx) {
+  if (!b || !ctx || which < 0 || which > 1) return CSM_ERR_INVALID_ARG;
+  *ctx = which ? b->ctx_coarse : b->ctx_stack;
+  return CSM_OK;
+}
+
 int csm_backend_scan_match(csm_backend* b, csm_gridmap* pub, const double cur[3], csm_backend_job* jobs,
                            int32_t n_jobs) {
   if (!b || !cur || n_jobs < 0 || (n_jobs > 0 && !jobs)) return CSM_ERR_INVALID_ARG;
@@ -179,7 +185,7 @@ int csm_backend_scan_match(csm_backend* b, csm_gridmap* pub, const double cur[3]
   int st;
   // per job: range data at each resolution, the rebuilt map pair, MapSizeCheck
   std::vector<std::vector<double>> cpts((size_t)n_jobs), fpts((size_t)n_jobs);
-  std::vector<csm_gridmap_state> fst((size_t)n_jobs);
+  std::vector<csm_gridmap_state> fst((size_t)n_jobs), cst((size_t)n_jobs);
   for (int32_t j = 0; j < n_jobs; ++j) {
     csm_backend_job& jb = jobs[j];
     scale_points(jb.points_m, jb.n_points, 1 / p.coarse_map_resolution, cpts[(size_t)j]);  // :268-272
@@ -191,18 +197,43 @@ int csm_backend_scan_match(csm_backend* b, csm_gridmap* pub, const double cur[3]
     for (int k = 0; k < 2; ++k)  // ScanMatchers::MapSizeCheck (scan_matchers.h:195-199)
       if ((st = csm::map_size_check(mp.map[k], jb.pose, p.range_max, p.levels[0].search_space_size)) != CSM_OK)
         return b->fail(st, "MapSizeCheck");
-    if ((st = csm_gridmap_get_state(mp.map[1], &fst[(size_t)j])) != CSM_OK) return st;
+    if ((st = csm_gridmap_get_state(mp.map[1], &fst[(size_t)j])) != CSM_OK ||
+        (st = csm_gridmap_get_state(mp.map[0], &cst[(size_t)j])) != CSM_OK)
+      return st;
     std::memcpy(jb.cov, (const double[9]){1, 0, 0, 0, 1, 0, 0, 0, 1}, sizeof(jb.cov));
     jb.score = 0.0;
     jb.optimize_cost = 0.0;
     jb.map_penalty = 1.0;
   }
   // correlative levels: all jobs in one batch over a stack of the fine maps
-  // when they share one geometry, else job by job
-  bool batch = n_jobs > 1 && !p.use_optimize_scan_match;
-  for (int32_t j = 1; batch && j < n_jobs; ++j)
+  // when they share one geometry, else job by job; with the Gauss-Newton
+  // matcher on, it runs first over a stack of the coarse maps, which then
+  // share one geometry too (a stack has one IsMapInit: the maps agree on it)
+  bool batch = n_jobs > 1;
+  for (int32_t j = 1; batch && j < n_jobs; ++j) {
     batch = same_geometry(fst[0], fst[(size_t)j]) && jobs[j].use_fine_scan_match == jobs[0].use_fine_scan_match;
-  if (batch) {
+    if (batch && p.use_optimize_scan_match)
+      batch = same_geometry(cst[0], cst[(size_t)j]) &&
+              (cst[0].map_update_index >= 0) == (cst[(size_t)j].map_update_index >= 0) &&
+              (fst[0].map_update_index >= 0) == (fst[(size_t)j].map_update_index >= 0);
+  }
+  if (batch && p.use_optimize_scan_match) {
+    const csm::MatchersConfig cfg{p.levels, p.use_optimize_scan_match, p.optimize_failed_cost, p.optimize,
+                                  p.range_max};
+    std::vector<csm_gridmap*> coarse((size_t)n_jobs), fine((size_t)n_jobs);
+    std::vector<csm::StackJob> sj((size_t)n_jobs);
+    for (int32_t j = 0; j < n_jobs; ++j) {
+      csm_backend_job& jb = jobs[j];
+      coarse[(size_t)j] = b->pairs[(size_t)j].map[0];
+      fine[(size_t)j] = b->pairs[(size_t)j].map[1];
+      sj[(size_t)j] = csm::StackJob{cpts[(size_t)j].data(), fpts[(size_t)j].data(), jb.n_points, jb.pose,
+                                    jb.cov,                 &jb.score,              &jb.optimize_cost};
+    }
+    std::string why;
+    if ((st = csm::scan_matchers_on_map_stacks(b->ctx_stack, b->ctx_coarse, coarse.data(), fine.data(), sj.data(),
+                                               n_jobs, cfg, jobs[0].use_fine_scan_match, &why)) != CSM_OK)
+      return b->fail(st, why);
+  } else if (batch) {
     std::vector<csm_gridmap*> fine((size_t)n_jobs);
     std::vector<double> pts, poses((size_t)n_jobs * 3), covs((size_t)n_jobs * 9), scores((size_t)n_jobs);
     std::vector<int64_t> off(1, 0);

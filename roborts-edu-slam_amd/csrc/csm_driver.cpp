@@ -26,8 +26,11 @@ struct BorrowedBatch {
 }  // namespace
 
 // csm_scan_matchers_loaded once locked, nothing pending, the staged batch taken.
-int csmh::matchers_loaded_locked(csm_ctx* c, const csm_param levels[3], int32_t use_fine, double* poses,
-                                 double* covs, double* scores) {
+// The seeded form (ScanMatchers::ScanMatch after its Gauss-Newton step,
+// scan_matchers.h:205-281): the levels from first_level on, each scan's running
+// sum started from score_seed and the seed counted as one term of the mean.
+int csmh::matchers_loaded_locked(csm_ctx* c, const csm_param all_levels[3], int32_t use_fine, double* poses,
+                                 double* covs, double* scores, int32_t first_level, const double* score_seed) {
   if (c->n_scans < 0) return c->fail(CSM_ERR_INVALID_ARG, "no scans loaded (csm_load_scans)");
   if (!c->has_grid) return c->fail(CSM_ERR_NO_GRID, "no grid set");
   const int32_t n_scans = c->n_scans;
@@ -38,7 +41,10 @@ int csmh::matchers_loaded_locked(csm_ctx* c, const csm_param levels[3], int32_t 
   // ScanMatchers::ScanMatch (scan_matchers.h:179-289), use_optimize = false:
   // coarse, then (use_fine) fine and super-fine, pose fed forward in place.
   std::vector<double> resp((size_t)n_scans, 0.0), sum((size_t)n_scans, 0.0);
-  const int n_levels = use_fine ? 3 : 1;
+  if (score_seed) sum.assign(score_seed, score_seed + n_scans);  // :211
+  const csm_param* levels = all_levels + first_level;
+  const int n_levels = use_fine ? 3 - first_level : 1;
+  const int times = n_levels + (score_seed ? 1 : 0);
   int st;
   bool fast = false;
   for (int l = 0; l < n_levels; ++l) fast |= levels[l].type == CSM_FAST;
@@ -58,7 +64,7 @@ int csmh::matchers_loaded_locked(csm_ctx* c, const csm_param levels[3], int32_t 
       for (int s = 0; s < n_scans; ++s) sum[(size_t)s] += resp[(size_t)s];
     }
   }
-  for (int s = 0; s < n_scans; ++s) scores[s] = sum[(size_t)s] / n_levels;  // :281
+  for (int s = 0; s < n_scans; ++s) scores[s] = sum[(size_t)s] / times;  // :281
   if (c->profiling) {
     c->t_exit = now_ms();
     c->account("host:call", (float)(c->t_exit - t_call), 0.0, 0.0);
@@ -208,6 +214,21 @@ int csm_scan_matchers_batch_grids(csm_ctx* c, int32_t n_scans, const double* pts
   if (st != CSM_OK) return st;
   if (grid_index) c->scan_grid.assign(grid_index, grid_index + n_scans);
   return matchers_loaded_locked(c, levels, use_fine, poses, covs, scores);
+}
+
+int csm_scan_matchers_batch_grids_seeded(csm_ctx* c, int32_t n_scans, const double* pts, const int64_t* offsets,
+                                         const int32_t* grid_index, const csm_param levels[3], int32_t first_level,
+                                         int32_t use_fine, const double* score_seed, double* poses, double* covs,
+                                         double* scores) {
+  if (!c || !levels || !poses || !covs || !scores) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  if (first_level < 0 || first_level > 1 || (first_level == 1 && !use_fine))
+    return c->fail(CSM_ERR_INVALID_ARG, "first_level must be 0, or 1 with use_fine");
+  int st = load_scans_locked(c, n_scans, pts, offsets);
+  if (st != CSM_OK) return st;
+  if (grid_index) c->scan_grid.assign(grid_index, grid_index + n_scans);
+  return matchers_loaded_locked(c, levels, use_fine, poses, covs, scores, first_level, score_seed);
 }
 
 }  // extern "C"

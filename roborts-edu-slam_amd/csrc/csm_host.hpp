@@ -569,6 +569,9 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState, csmh::Scan
   // Gauss-Newton matcher (csm_optimize_scan_match*): per-scan state up, sums down
   csmh::DevBuf opt_off, opt_scans, opt_sums;
   csmh::HostBuf h_opt_scans, h_opt_sums;
+  // ... and the one-launch solve's block (optimize_batch_device): states, offsets, grid indices
+  csmh::DevBuf opt_solve;
+  csmh::HostBuf h_opt_solve;
 
   csmh::DevBuf gstats;  // ensure_int_grid's whole-grid statistics
   // Changes whenever the current fixed-point grid may have (rebuilt, cells or
@@ -875,8 +878,7 @@ int match_level(csm_ctx* c, int32_t n_scans, const int64_t* offsets, const csm_p
                 const int32_t* scan_grid = nullptr, int skip_lists = 0);
 
 // csm_optimize_host.cpp
-constexpr double kOptCostPointSize = 1000;                // optimize_scan_matcher.h:234
-constexpr double kOptMaxCost = 1.0 * kOptCostPointSize;   // :235
+constexpr double kOptMaxCost = 1.0 * csm::opt::kCostPointSize;  // optimize_scan_matcher.h:235
 
 inline bool map_ready(const csm_ctx* c) { return c->has_grid && c->info.update_index >= 0; }
 
@@ -896,7 +898,8 @@ int ranges_ingest(csm_ctx* c, csm_ctx::Staged& S, const csm_laser& L, double thr
 // csm_deskew.cpp: the scans a de-skewed batch's kernel flagged, de-skewed on the host (take_staged, after S.ready)
 int repair_deskewed(csm_ctx* c, csm_ctx::Staged& S);
 // csm_driver.cpp
+// first_level / score_seed: csm_scan_matchers_batch_grids_seeded (0 and null: the plain forms)
 int matchers_loaded_locked(csm_ctx* c, const csm_param levels[3], int32_t use_fine, double* poses, double* covs,
-                           double* scores);
+                           double* scores, int32_t first_level = 0, const double* score_seed = nullptr);
 
 }  // namespace csmh

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime_api.h>
 #include <cstdint>
 
+#include "csm_optimize_step.hpp"
+
 namespace csm {
 
 // One window to search: a scan (its points) at one level, centred on one pose.
@@ -564,7 +566,7 @@ hipError_t launch_update_cells(const CellUpdate* d_updates, int64_t n, float* g,
 struct OptScan {
   double c, s, tx, ty;
   int32_t active;
-  int32_t pad;
+  int32_t grid;  // which resident grid of the stack the scan reads
 };
 // Sums of UpdateCost (optimize_scan_matcher.h:154-221) in point order:
 // v = {cost, H00, H10, H11, H20, H21, H22, b0, b1, b2}; valid = points in map.
@@ -584,6 +586,29 @@ struct OptArgs {
   OptSums* out;
 };
 hipError_t launch_optimize_cost(const OptArgs& A, int32_t n_scans, hipStream_t stream);
+// The whole solve in one launch (optimize_solve_kernel): per scan the
+// map-cell estimate in and out, the cost, the UpdateCost evaluations made and
+// the state (csm_optimize_step.hpp: kRun in; kDone, kNan or kHost out; any
+// other state in: the scan is left alone).
+struct OptSolveScan {
+  double est[3];
+  double cost;
+  int32_t iters;
+  int32_t state;
+};
+struct OptSolveArgs {
+  const float* grid;  // packed fp32 grids of one geometry, back to back
+  int32_t size_x, size_y;
+  float outside;
+  int32_t iterate_max_times;
+  const double* pts;
+  const int64_t* offsets;
+  const int32_t* grid_index;  // per scan (nullable: grid 0)
+  const double* tab;          // libm's sincos table on the device (libm_sincos.hpp)
+  opt::StepParam P;
+  OptSolveScan* scans;
+};
+hipError_t launch_optimize_solve(const OptSolveArgs& A, int32_t n_scans, hipStream_t stream);
 
 // Reduce per-window partials (blocks_per_scan each) to one BestPartial per window.
 hipError_t launch_reduce_best(const BestPartial* d_partials, int32_t blocks_per_scan,

@@ -4,6 +4,7 @@
 #include "csm_matchers.hpp"
 
 #include <cstring>
+#include <vector>
 
 namespace csm {
 
@@ -68,6 +69,69 @@ int scan_matchers_on_maps(csm_ctx* fine_ctx, csm_ctx* coarse_ctx, csm_gridmap* c
   }
   std::memcpy(pose, process, sizeof(process));
   *score = sum / times;  // :281
+  return CSM_OK;
+}
+
+int scan_matchers_on_map_stacks(csm_ctx* fine_ctx, csm_ctx* coarse_ctx, csm_gridmap* const* coarse_maps,
+                                csm_gridmap* const* fine_maps, StackJob* jobs, int32_t n_jobs,
+                                const MatchersConfig& cfg, int use_fine, std::string* err) {
+  auto fail = [&](int st, const char* what, csm_ctx* c) {
+    if (err) *err = std::string(what) + (c ? std::string(": ") + csm_last_error(c) : std::string());
+    return st;
+  };
+  if (!coarse_ctx) return fail(CSM_ERR_INVALID_ARG, "Gauss-Newton matcher without a coarse context", nullptr);
+  if (n_jobs <= 0) return CSM_OK;
+  int st;
+  const size_t n = (size_t)n_jobs;
+  // the Gauss-Newton matcher of every job on its coarse map, one launch (:205-211)
+  std::vector<double> pts, process(n * 3), cost(n, 0.0);
+  std::vector<int64_t> off(1, 0);
+  std::vector<int32_t> gidx(n);
+  for (size_t j = 0; j < n; ++j) {
+    pts.insert(pts.end(), jobs[j].coarse_pts, jobs[j].coarse_pts + 2 * (size_t)jobs[j].n);
+    off.push_back(off.back() + jobs[j].n);
+    gidx[j] = (int32_t)j;
+    std::memcpy(&process[3 * j], jobs[j].pose, sizeof(double) * 3);
+  }
+  if ((st = csm_set_grid_stack_gridmaps(coarse_ctx, coarse_maps, n_jobs)) != CSM_OK ||
+      (st = csm_optimize_scan_match_batch_grids(coarse_ctx, n_jobs, pts.data(), off.data(), gidx.data(),
+                                                &cfg.optimize, process.data(), cost.data(), nullptr)) != CSM_OK)
+    return fail(st, "csm_optimize_scan_match_batch_grids", coarse_ctx);
+  for (size_t j = 0; j < n; ++j) *jobs[j].opt_cost = cost[j];
+  if ((st = csm_set_grid_stack_gridmaps(fine_ctx, fine_maps, n_jobs)) != CSM_OK)
+    return fail(st, "csm_set_grid_stack_gridmaps", fine_ctx);
+  // group 0 (:224-242): the matcher failed or !use_fine, every level from the
+  // original pose; group 1: fine and super-fine from the Gauss-Newton pose,
+  // its score one term of the mean (:211)
+  for (int grp = 0; grp < 2; ++grp) {
+    std::vector<int32_t> who;
+    for (size_t j = 0; j < n; ++j) {
+      if ((!use_fine || cost[j] > cfg.optimize_failed_cost) == (grp == 0)) who.push_back((int32_t)j);
+    }
+    if (who.empty()) continue;
+    const size_t m = who.size();
+    std::vector<double> gpts, poses(m * 3), covs(m * 9), seed(m), scores(m, 0.0);
+    std::vector<int64_t> goff(1, 0);
+    for (size_t k = 0; k < m; ++k) {
+      const StackJob& J = jobs[(size_t)who[k]];
+      gpts.insert(gpts.end(), J.fine_pts, J.fine_pts + 2 * (size_t)J.n);
+      goff.push_back(goff.back() + J.n);
+      std::memcpy(&poses[3 * k], grp == 0 ? J.pose : &process[3 * (size_t)who[k]], sizeof(double) * 3);
+      std::memcpy(&covs[9 * k], J.cov, sizeof(double) * 9);
+      seed[k] = cfg.optimize_failed_cost / (cost[(size_t)who[k]] + cfg.optimize_failed_cost);  // :211
+    }
+    if ((st = csm_scan_matchers_batch_grids_seeded(fine_ctx, (int32_t)m, gpts.data(), goff.data(), who.data(),
+                                                   cfg.levels, grp, grp == 0 ? use_fine : 1,
+                                                   grp == 0 ? nullptr : seed.data(), poses.data(), covs.data(),
+                                                   scores.data())) != CSM_OK)
+      return fail(st, "csm_scan_matchers_batch_grids_seeded", fine_ctx);
+    for (size_t k = 0; k < m; ++k) {
+      StackJob& J = jobs[(size_t)who[k]];
+      std::memcpy(J.pose, &poses[3 * k], sizeof(double) * 3);
+      std::memcpy(J.cov, &covs[9 * k], sizeof(double) * 9);
+      *J.score = scores[k];
+    }
+  }
   return CSM_OK;
 }
 

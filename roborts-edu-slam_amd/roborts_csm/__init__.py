@@ -505,6 +505,54 @@ class Context:
                                                        iters.ctypes.data_as(C.POINTER(C.c_int32))))
         return costs, iters
 
+    def optimize_scan_match_batch_grids(self, points, offsets, grid_index, param, poses):
+        """csm_optimize_scan_match_batch_grids: optimize_scan_match_batch with scan
+        i on grid grid_index[i] of the resident stack (None: grid 0), the whole
+        solve in one launch. Returns (costs, iterations); poses updated in place."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = off.size - 1
+        assert poses.dtype == np.float64 and poses.flags.c_contiguous and poses.size == 3 * n
+        gi = None if grid_index is None else np.ascontiguousarray(grid_index, dtype=np.int32)
+        assert gi is None or gi.size == n
+        p = param if isinstance(param, _abi.CsmOptimizeParam) else param.to_c()
+        costs = np.zeros(n)
+        iters = np.zeros(n, dtype=np.int32)
+        self._loaded = None  # host points replace the loaded set (include/csm.h)
+        self._check(_lib.csm_optimize_scan_match_batch_grids(
+            self._h, n, _dptr(pts), _i64ptr(off), None if gi is None else gi.ctypes.data_as(_abi._i32p), C.byref(p),
+            _dptr(poses), _dptr(costs), iters.ctypes.data_as(_abi._i32p)))
+        return costs, iters
+
+    def scan_matchers_batch_grids_seeded(self, points, offsets, grid_index, levels, poses, covs, first_level: int = 0,
+                                         use_fine: bool = True, score_seed=None):
+        """csm_scan_matchers_batch_grids_seeded: levels[first_level:] of the 3-level
+        driver, scan i on grid grid_index[i] (None: grid 0); score_seed (None:
+        no seed) starts each scan's sum and counts as one term of the mean.
+        Returns the scores; poses and covs updated in place."""
+        pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+        off = np.ascontiguousarray(offsets, dtype=np.int64)
+        n = off.size - 1
+        assert poses.dtype == np.float64 and poses.flags.c_contiguous and poses.size == 3 * n
+        assert covs.dtype == np.float64 and covs.flags.c_contiguous and covs.size == 9 * n
+        gi = None if grid_index is None else np.ascontiguousarray(grid_index, dtype=np.int32)
+        assert gi is None or gi.size == n
+        seed = None if score_seed is None else np.ascontiguousarray(score_seed, dtype=np.float64)
+        assert seed is None or seed.size == n
+        scores = np.zeros(n)
+        lv = (CsmParam * 3)(*[_as_param(l) for l in levels])
+        queued = self.__dict__.get("_queued")  # a synchronous load drops queued batches (after the call)
+        self._loaded = (n, pts, off)  # it is the loaded set now
+        try:
+            self._check(_lib.csm_scan_matchers_batch_grids_seeded(
+                self._h, n, _dptr(pts), _i64ptr(off), None if gi is None else gi.ctypes.data_as(_abi._i32p), lv,
+                int(first_level), 1 if use_fine else 0, None if seed is None else _dptr(seed), _dptr(poses),
+                _dptr(covs), _dptr(scores)))
+        finally:
+            if queued is not None and self.__dict__.get("_queued") is queued:
+                self.__dict__.pop("_queued", None)
+        return scores
+
     def optimize_update_cost(self, points_cells, est_map):
         """One device UpdateCost at a map-cell pose -> (cost, H 3x3, b) (test hook)."""
         pts = np.ascontiguousarray(points_cells, dtype=np.float64).reshape(-1, 2)

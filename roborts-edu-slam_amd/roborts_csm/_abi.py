@@ -36,6 +36,7 @@ EXPORTED = (
     "csm_set_profiling", "csm_kernel_stats", "csm_sort_order", "csm_phase_buckets",
     "csm_set_grid_stack", "csm_best_windows", "csm_optimize_scan_match", "csm_optimize_scan_match_batch",
     "csm_optimize_update_cost", "csm_load_scans_grids", "csm_scan_matchers_batch_grids",
+    "csm_optimize_scan_match_batch_grids", "csm_scan_matchers_batch_grids_seeded",
     "csm_search_windows", "csm_search_bounds", "csm_host_plan_compute", "csm_get_host_plan",
     "csm_search_match", "csm_search_collect", "csm_list_select",
     # include/csm_gridmap.h
@@ -53,7 +54,7 @@ EXPORTED = (
     "csm_loop_closure_set_submaps", "csm_loop_closure_match", "csm_loop_closure_match_full",
     # include/csm_backend.h
     "csm_backend_create", "csm_backend_destroy", "csm_backend_last_error", "csm_backend_add_scan",
-    "csm_backend_set_scan_pose", "csm_backend_scan_match", "csm_backend_map",
+    "csm_backend_set_scan_pose", "csm_backend_scan_match", "csm_backend_map", "csm_backend_matcher",
 )
 
 PROBABILITY_CELL, COUNT_CELL = 0, 1
@@ -322,6 +323,8 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "csm_optimize_scan_match": (C.c_int, [_ctx, _dp, C.c_int32, C.POINTER(CsmOptimizeParam), _dp, _dp]),
         "csm_optimize_scan_match_batch": (C.c_int, [_ctx, C.c_int32, _dp, _i64p, C.POINTER(CsmOptimizeParam), _dp,
                                                     _dp, _i32p]),
+        "csm_optimize_scan_match_batch_grids": (C.c_int, [_ctx, C.c_int32, _dp, _i64p, _i32p,
+                                                          C.POINTER(CsmOptimizeParam), _dp, _dp, _i32p]),
         "csm_optimize_update_cost": (C.c_int, [_ctx, _dp, C.c_int32, _dp, _dp, _dp, _dp]),
         "csm_gridmap_create": (C.c_int, [C.c_int, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_double,
                                          C.c_double, C.c_double, C.c_float, C.POINTER(C.c_void_p)]),
@@ -355,6 +358,8 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "csm_load_scans_grids": (C.c_int, [_ctx, C.c_int32, _dp, _i64p, _i32p]),
         "csm_scan_matchers_batch_grids": (C.c_int, [_ctx, C.c_int32, _dp, _i64p, _i32p, C.POINTER(CsmParam), C.c_int32,
                                                     _dp, _dp, _dp]),
+        "csm_scan_matchers_batch_grids_seeded": (C.c_int, [_ctx, C.c_int32, _dp, _i64p, _i32p, C.POINTER(CsmParam),
+                                                           C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
         "csm_set_grid_stack_gridmaps": (C.c_int, [_ctx, C.POINTER(C.c_void_p), C.c_int32]),
         "csm_loop_closure_create": (C.c_int, [C.c_int32, _i32p, C.POINTER(C.c_void_p)]),
         "csm_loop_closure_destroy": (C.c_int, [C.c_void_p]),
@@ -372,6 +377,7 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "csm_backend_set_scan_pose": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
         "csm_backend_scan_match": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_void_p, C.c_int32]),
         "csm_backend_map": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+        "csm_backend_matcher": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -166,6 +166,16 @@ class ScanMatchService:
         best_pose[:] = r.pose
         return r.score, r.cov
 
+    FINE_MATCHER, COARSE_MATCHER = 0, 1
+
+    def matcher(self, which: int):
+        """csm_backend_matcher: the batched path's matcher context (0 the fine
+        stack's, 1 the coarse one's), borrowed; None when the service has none."""
+        from . import Context
+        h = C.c_void_p()
+        self._check(_lib.csm_backend_matcher(self._h, int(which), C.byref(h)))
+        return Context.borrow(h, self) if h.value else None
+
     def map(self, slot: int, which: int):
         from .frontend import _BorrowedMap
         h = C.c_void_p()
