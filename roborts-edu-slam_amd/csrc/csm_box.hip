@@ -96,6 +96,7 @@ struct BoxWave {
   // a beam point's byte offset step: full-rate 24-bit multiplies (the host
   // keeps every scan under 2^24 points and step * 16 under 2^24: box_points_ok)
   uint32_t step16 = (uint32_t)step * 16u;
+  int bg_tiles8 = 0;  // the map of uniform boxes (offsets<.., true>): bytes per row of 8 x 8 tiles
 
   // The box test of one beam point; on success (ix0, iy0) is the box corner.
   // far: every cell the beam reads for this wave's candidates is off the
@@ -128,8 +129,10 @@ struct BoxWave {
   // row piece: copy c = -(ix0 / 4) mod 4 puts cells (ix0 & ~3) .. +15 in one
   // 16-byte strip row, and the corner's byte phase ix0 & 3 rides in the low
   // bits (the piece itself is 16-byte aligned).
-  template <bool STRIP = false>
-  __device__ __forceinline__ int offsets(const double2 p, int cb, uint64_t& slow) const {
+  // BG: *bgkey is the corner's place in the map of uniform boxes, byte offset
+  // << 3 | bit of the byte (bg_dropped), 0 for a lane that reads the zero block.
+  template <bool STRIP = false, bool BG = false>
+  __device__ __forceinline__ int offsets(const double2 p, int cb, uint64_t& slow, uint32_t* bgkey = nullptr) const {
     double lx, ly;
     int ix0, iy0;
     bool far;
@@ -149,7 +152,22 @@ struct BoxWave {
     } else {
       o = iy0 * pitch4 + (ix0 << cell_shift);
     }
-    return (live && clean && ix0 < sx + pad && iy0 < sy + pad) ? o : zero_off;
+    const bool in = live && clean && ix0 < sx + pad && iy0 < sy + pad;
+    if constexpr (BG)
+      *bgkey = in ? ((uint32_t)((iy0 >> 3) * bg_tiles8 + (ix0 & ~7) + (iy0 & 7)) << 3) | (uint32_t)(ix0 & 7) : 0u;
+    return in ? o : zero_off;
+  }
+  // The map's byte of a key, and whether it drops the beam: its whole box
+  // holds the background value, which the kernel adds once per dropped beam
+  // (n counts them, wave-uniform). A dropped beam reads the zero block like a
+  // box wholly past the grid.
+  static __device__ __forceinline__ uint32_t bg_byte(__amdgpu_buffer_rsrc_t map, uint32_t key) {
+    return (uint32_t)__builtin_amdgcn_raw_buffer_load_b8(map, (int)(key >> 3), 0, 0);
+  }
+  __device__ __forceinline__ int bg_dropped(int off, uint32_t key, uint32_t byte, int& n) const {
+    const bool drop = off != zero_off && ((byte >> (key & 7u)) & 1u) != 0;
+    n += __builtin_popcountll(__builtin_amdgcn_ballot_w64(drop));
+    return drop ? zero_off : off;
   }
   __device__ __forceinline__ double2 point(int cb) const {
     const uint32_t i = (uint32_t)min(cb + lane, n_used - 1);
@@ -162,9 +180,15 @@ struct BoxWave {
   // runs of boxes wholly off the grid and of rejected beams are dropped (they
   // read zeros). Slots from `scratch` on take the non-run lanes' writes
   // (branch-free). Returns the run count.
-  template <int PF = kPF, typename CT = int32_t, bool STRIP = false, bool ILP = false>
+  // BG (with ILP): the chunks' bytes of the map of uniform boxes are issued
+  // once their corners are known, ahead of the next chunks' points, and read
+  // where the run edges are found; nbg counts the beams they drop.
+  template <int PF = kPF, typename CT = int32_t, bool STRIP = false, bool ILP = false, bool BG = false>
   __device__ __forceinline__ int build_runs(int s0, int s1, int32_t* run_off, CT* run_cnt, int scratch,
-                                            uint64_t& slow) const {
+                                            uint64_t& slow,
+                                            __amdgpu_buffer_rsrc_t bgmap = dev::uniform_rsrc(nullptr, 0),
+                                            int* nbg = nullptr) const {
+    static_assert(!BG || ILP, "the map's reads ride on the ILP form");
     int nruns = 0;
     // points of PF chunks in flight: the list build is latency-bound
     // otherwise (one dependent load per 64 beams)
@@ -179,9 +203,18 @@ struct BoxWave {
       // the compiler interleaves), then the next PF chunks' points are issued
       // and the run edges found while they are in flight
       int offv[PF];
+      uint32_t bgk[PF], bgb[PF];
       if constexpr (ILP) {
 #pragma unroll
-        for (int u = 0; u < PF; ++u) offv[u] = offsets<STRIP>(pq[u], cb0 + 64 * u, slow);
+        for (int u = 0; u < PF; ++u) {
+          offv[u] = offsets<STRIP, BG>(pq[u], cb0 + 64 * u, slow, &bgk[u]);
+          // each chunk's byte as soon as its corners are known: the later
+          // chunks' box tests cover its latency
+          if constexpr (BG) {
+            bgb[u] = bg_byte(bgmap, bgk[u]);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+        }
 #pragma unroll
         for (int u = 0; u < PF; ++u) pq[u] = point(cb0 + 64 * (u + PF));
         __builtin_amdgcn_sched_barrier(0);
@@ -195,6 +228,8 @@ struct BoxWave {
         int off;
         if constexpr (ILP) {
           off = offv[u];
+          // (a chunk at or past s1 is the next segment's: not counted here)
+          if constexpr (BG) off = bg_dropped(cb + lane < s1 ? off : zero_off, bgk[u], bgb[u], *nbg);
         } else {
           const double2 pcur = pq[u];
           pq[u] = point(cb + 64 * PF);
@@ -480,7 +515,13 @@ __device__ __forceinline__ uint32_t byte_x8(uint32_t w) {
 // 2p + 1 of the segment, in beam order. The sums are the same exact integers.
 constexpr int kPairNoRunBeams = 128;
 
-template <int NS, bool BEST, bool NORUN = false>
+// BG: the grid has a map of uniform boxes (L.bg_map, csm_internal.hpp BgGeom).
+// A beam whose whole box holds the background value V adds V to every
+// candidate: it is dropped from the lists like a box past the grid, counted,
+// and count * V joins the integer sums once, before the cell-by-cell pass. The
+// sums are exact integers either way, so the scores are the same bits. The
+// run-free form then packs the beams it keeps (pairs in beam order still).
+template <int NS, bool BEST, bool NORUN = false, bool BG = false>
 __global__ CSM_PAIR_BOUNDS void score_box_pair_kernel(LevelWork L, const ScanWork* __restrict__ scans,
                                                             const double2* __restrict__ pts,
                                                             const AngleEntry* __restrict__ angles,
@@ -504,6 +545,16 @@ __global__ CSM_PAIR_BOUNDS void score_box_pair_kernel(LevelWork L, const ScanWor
   BoxWave B{S, ae, pts + S.pts_off, S.step, S.n_used, lane, L.size_x, L.size_y, 0, zero_off, S.x0 /* :569 */,
             S.y0 /* :572 */, 0, L.strip_bytes, L.strip_copy_bytes, NS, kStripPadLo};
   const int n_used = S.n_used;
+  // the map of uniform boxes of this window's grid, the background's value
+  // and the beams dropped for it (wave-uniform)
+  const __amdgpu_buffer_rsrc_t bgmap = dev::uniform_rsrc(
+      BG ? L.bg_map + (int64_t)S.grid_index * L.bg_grid_bytes : nullptr, BG ? L.bg_grid_bytes : 0);
+  int64_t bg_val = 0;
+  int nbg = 0;
+  if constexpr (BG) {
+    B.bg_tiles8 = L.bg_tiles8;
+    bg_val = L.pal_vals[L.bg_info[S.grid_index * kBgInfoInts + kBgInfoBg] & (kPairMaxPal - 1)];
+  }
   // pair table: tab[a | b << sh] = V[a] + V[b]
   const int sh = L.pal_n <= 8 ? 3 : 4;
   __shared__ double tab[256];
@@ -543,6 +594,29 @@ __global__ CSM_PAIR_BOUNDS void score_box_pair_kernel(LevelWork L, const ScanWor
       // beam i of the segment's box offset at pair_off[i]; past the segment,
       // through the look-ahead step's pairs, the zero run
       const int s1 = min(n_used, s0 + kPairSeg);
+      int nkept = s1 - s0;
+      if constexpr (BG) {
+        // the beams that read a box, packed in beam order; then the zero run
+        // through the look-ahead step's pairs
+        nkept = 0;
+        for (int cb = s0; cb < s1; cb += 128) {
+          const double2 p0 = B.point(cb), p1 = B.point(cb + 64);
+          uint32_t k0, k1;
+          int o[2] = {B.offsets<true, true>(p0, cb, slow, &k0), B.offsets<true, true>(p1, cb + 64, slow, &k1)};
+          const uint32_t b0 = BoxWave::bg_byte(bgmap, k0), b1 = BoxWave::bg_byte(bgmap, k1);
+          o[0] = B.bg_dropped(cb + lane < s1 ? o[0] : zero_off, k0, b0, nbg);
+          o[1] = B.bg_dropped(cb + 64 + lane < s1 ? o[1] : zero_off, k1, b1, nbg);
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const bool keep = o[h] != zero_off;
+            const uint64_t K = __builtin_amdgcn_ballot_w64(keep);
+            if (keep) pair_off[nkept + __builtin_popcountll(K & dev::below_mask(lane))] = o[h];
+            nkept += __builtin_popcountll(K);
+          }
+        }
+        npad = ((nkept + 1) / 2 + kStepPairs - 1) / kStepPairs * kStepPairs;
+        for (int i = nkept + lane; i < 2 * (npad + kStepPairs); i += 64) pair_off[i] = zero_off;
+      } else {
       npad = ((s1 - s0 + 1) / 2 + kStepPairs - 1) / kStepPairs * kStepPairs;
       const int s_end = s0 + 2 * (npad + kStepPairs);
       for (int cb = s0; cb < s_end; cb += 128) {
@@ -552,16 +626,17 @@ __global__ CSM_PAIR_BOUNDS void score_box_pair_kernel(LevelWork L, const ScanWor
         pair_off[cb - s0 + lane] = cb + lane < s1 ? o0 : zero_off;
         if (cb + 64 < s_end) pair_off[cb + 64 - s0 + lane] = cb + 64 + lane < s1 ? o1 : zero_off;
       }
+      }
       __syncthreads();
 #ifdef CSM_BOX_TRACE
       tr[2] += BOX_STAMP() - tq;
       tq = BOX_STAMP();
-      tr[8] += s1 - s0;
+      tr[8] += nkept;
       tr[9] += npad;
 #endif
     } else {
-    const int nruns = B.build_runs<CSM_PAIR_PF, uint8_t, true, CSM_PAIR_ILP != 0>(
-        s0, min(n_used, s0 + kPairSeg), run_off, run_cnt, kScratch, slow);
+    const int nruns = B.build_runs<CSM_PAIR_PF, uint8_t, true, CSM_PAIR_ILP != 0, BG>(
+        s0, min(n_used, s0 + kPairSeg), run_off, run_cnt, kScratch, slow, bgmap, &nbg);
     bin[lane] = 0;
     __syncthreads();
 #ifdef CSM_BOX_TRACE
@@ -691,6 +766,10 @@ __global__ CSM_PAIR_BOUNDS void score_box_pair_kernel(LevelWork L, const ScanWor
   int64_t mine[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) mine[t] = (kk < NS && 4 * q + t < NS) ? xch[kk * 16 + 4 * q + t] : 0;
+  if constexpr (BG) {  // the dropped beams' share, the same for every candidate
+#pragma unroll
+    for (int t = 0; t < 4; ++t) mine[t] += (int64_t)nbg * bg_val;
+  }
   const int32_t* gi = L.gridi + (int64_t)S.grid_index * L.gridi_stride;
 #ifdef CSM_BOX_TRACE
   tr[5] = BOX_STAMP();
@@ -723,15 +802,16 @@ template <int NS>
 hipError_t launch_pair(const LevelWork& L, const ScanWork* s, const double2* p, const AngleEntry* an, double* out,
                        BestPartial* part, unsigned nblk, hipStream_t stream) {
   const bool norun = L.max_n_used > 0 && L.max_n_used <= kPairNoRunBeams;
+  const bool bg = L.bg_map != nullptr;
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(nblk), dim3(64), 0, stream, L, s, p, an, out, part); };
   if (part && norun)
-    hipLaunchKernelGGL((score_box_pair_kernel<NS, true, true>), dim3(nblk), dim3(64), 0, stream, L, s, p, an, out, part);
+    bg ? go(score_box_pair_kernel<NS, true, true, true>) : go(score_box_pair_kernel<NS, true, true>);
   else if (part)
-    hipLaunchKernelGGL((score_box_pair_kernel<NS, true>), dim3(nblk), dim3(64), 0, stream, L, s, p, an, out, part);
+    bg ? go(score_box_pair_kernel<NS, true, false, true>) : go(score_box_pair_kernel<NS, true>);
   else if (norun)
-    hipLaunchKernelGGL((score_box_pair_kernel<NS, false, true>), dim3(nblk), dim3(64), 0, stream, L, s, p, an, out,
-                       part);
+    bg ? go(score_box_pair_kernel<NS, false, true, true>) : go(score_box_pair_kernel<NS, false, true>);
   else
-    hipLaunchKernelGGL((score_box_pair_kernel<NS, false>), dim3(nblk), dim3(64), 0, stream, L, s, p, an, out, part);
+    bg ? go(score_box_pair_kernel<NS, false, false, true>) : go(score_box_pair_kernel<NS, false>);
   return hipGetLastError();
 }
 
@@ -760,6 +840,12 @@ hipError_t launch_score_box_pair(const LevelWork& L, const ScanWork* d_scans, co
       L.strip_bytes != G.strip_bytes || L.strip_copy_bytes != G.copy_bytes || L.strip_grid_bytes != G.grid_bytes ||
       G.grid_bytes > INT32_MAX || (int64_t)L.size_y * 16 > INT32_MAX)
     return hipErrorInvalidValue;
+  if (L.bg_map) {  // the map's geometry is this grid's, its byte offsets fit a key
+    const BgGeom BG = bg_geom(L.size_x, L.size_y);
+    if (!L.bg_info || L.bg_tiles8 != BG.tiles_x * 8 || L.bg_grid_bytes != BG.grid_bytes ||
+        BG.grid_bytes >= (1 << 28))
+      return hipErrorInvalidValue;
+  }
   const double2* p = reinterpret_cast<const double2*>(d_pts);
   const unsigned n = (unsigned)nblk;
   switch (ns) {

@@ -178,6 +178,14 @@ void note_new_values(csm_ctx* c, const PackStats& ps) {
   c->int_max_abs = std::max(c->int_max_abs, (double)ps.max_abs);
 }
 
+// The share of set bits in the map of uniform boxes below which the pair
+// kernel does not read it. The read costs the same whatever it finds: with an
+// empty map forced on, the headline step is 0.060 ms longer; with config 2's
+// map (38 % of corners set) it is 0.149 ms shorter than that. Taking the gain
+// as proportional to the share, the two meet at 0.38 * 0.060 / 0.149 = 0.15
+// (profiles/background_runs/speed.md).
+constexpr double kBgMinShare = 0.16;
+
 // The palette copy of the current gridi (csm_palette.hip), built once per
 // grid generation: the grid's distinct fixed-point values and a byte per cell
 // holding its value's index, read by the v10 palette box kernel. A grid with
@@ -205,6 +213,8 @@ int ensure_palette(csm_ctx* c) {
     return c->hip_fail(e, "palette size");
   c->pal_n = (m >= 1 && m <= csm::kPalMax) ? m : 0;
   c->pal_strips_ok = false;
+  c->bg_ok = c->bg5_ok = false;
+  c->bg_share = c->bg5_share = 0.0;
   const csm::StripGeom SG = csm::strip_geom(c->info.size_x, c->info.size_y);
   // (the pair kernel's strip offsets are 24-bit products: strips under 2^24 bytes)
   if (c->pair_kernel && c->pal_n >= 1 && c->pal_n <= csm::kPairMaxPal && SG.grid_bytes <= INT32_MAX &&
@@ -215,9 +225,46 @@ int ensure_palette(csm_ctx* c) {
     if ((e = csm::launch_build_strips((const uint8_t*)c->pal_grid.p, c->pitch, c->info.size_x, c->info.size_y,
                                       idx_stride, c->n_grids, (uint8_t*)c->pal_strips.p, c->stream)) != hipSuccess)
       return c->hip_fail(e, "pal_strips_kernel");
+    // the map of uniform boxes, from the same index grid (byte offsets and the
+    // corner's bit in one 32-bit key: maps under 2^28 bytes)
+    const csm::BgGeom BG = csm::bg_geom(c->info.size_x, c->info.size_y);
+    const bool bg_build = c->bg_runs != 0 && BG.grid_bytes < (1 << 28) && c->n_grids <= 65535;
+    std::vector<int32_t> bg_info((size_t)c->n_grids * csm::kBgInfoInts);
+    if (bg_build) {
+      if ((e = c->bg_map.ensure((size_t)BG.grid_bytes * (size_t)c->n_grids)) != hipSuccess ||
+          (e = c->bg_map5.ensure((size_t)BG.grid_bytes * (size_t)c->n_grids)) != hipSuccess ||
+          (e = c->bg_info.ensure(bg_info.size() * sizeof(int32_t))) != hipSuccess)
+        return c->hip_fail(e, "hipMalloc(background map)");
+      if ((e = csm::launch_build_bg_map((const uint8_t*)c->pal_grid.p, c->pitch, c->info.size_x, c->info.size_y,
+                                        idx_stride, c->n_grids, (int32_t*)c->bg_info.p, (uint8_t*)c->bg_map.p,
+                                        (uint8_t*)c->bg_map5.p, c->stream)) != hipSuccess)
+        return c->hip_fail(e, "bg_map_kernel");
+      if (c->bg_runs == 3 &&
+          ((e = hipMemsetAsync(c->bg_map.p, 0, (size_t)BG.grid_bytes * (size_t)c->n_grids, c->stream)) != hipSuccess ||
+           (e = hipMemsetAsync(c->bg_map5.p, 0, (size_t)BG.grid_bytes * (size_t)c->n_grids, c->stream)) != hipSuccess))
+        return c->hip_fail(e, "hipMemsetAsync(background map)");
+      if ((e = hipMemcpyAsync(bg_info.data(), c->bg_info.p, bg_info.size() * sizeof(int32_t), hipMemcpyDeviceToHost,
+                              c->stream)) != hipSuccess)
+        return c->hip_fail(e, "hipMemcpyAsync(background map)");
+    }
     // other parts' streams read the strips next (like gridi)
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hip_fail(e, "hipStreamSynchronize(strips)");
     c->pal_strips_ok = true;
+    if (bg_build) {
+      double set = 0.0, set5 = 0.0;
+      for (int gi = 0; gi < c->n_grids; ++gi) {
+        set += (double)(uint32_t)bg_info[(size_t)gi * csm::kBgInfoInts + csm::kBgInfoSet];
+        set5 += (double)(uint32_t)bg_info[(size_t)gi * csm::kBgInfoInts + csm::kBgInfoSet5];
+      }
+      c->bg_share = set / ((double)BG.grid_bytes * 8.0 * c->n_grids);
+      c->bg5_share = set5 / ((double)BG.grid_bytes * 8.0 * c->n_grids);
+      c->bg_ok = c->bg_runs >= 2 || c->bg_share >= kBgMinShare;
+      c->bg5_ok = c->bg_runs >= 2 || c->bg5_share >= kBgMinShare;
+      if (c->profiling) {
+        c->account("grid:bg_map", 0.f, (double)BG.grid_bytes * c->n_grids, set);
+        c->account("grid:bg_map5", 0.f, (double)BG.grid_bytes * c->n_grids, set5);
+      }
+    }
   }
   c->pal_gen = c->grid_gen;
   c->pal_src = c->d_gridi;

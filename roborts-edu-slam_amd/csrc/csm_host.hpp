@@ -419,8 +419,9 @@ struct LaunchSlot {
 };
 
 // A resident grid: the context is one (the current grid) and parks others in
-// csm_ctx::parked; swap_grid exchanges them whole. The palette and the strip
-// copies are the context's, keyed on grid_gen, not part of this.
+// csm_ctx::parked; swap_grid exchanges them whole. The palette, the strip
+// copies and the maps of uniform boxes (which hold the palette's indices) are
+// the context's, keyed on grid_gen, not part of this.
 struct GridState {
   csm_map_info info{};
   bool has_grid = false;
@@ -526,6 +527,19 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState, csmh::Scan
   int32_t pal_n = 0;           // palette size (0: none, e.g. more than kPalMax values)
   uint64_t pal_gen = 0;        // grid_gen the palette was built for
   const int32_t* pal_src = nullptr;  // ... and the gridi it was built from
+  // The pair kernel's map of uniform boxes (csm_palette.hip bg_geom), built
+  // with the strips and keyed like them. bg_ok: the pair kernel uses it (the
+  // share of set bits is at least kBgMinShare, or the knob forces it).
+  // CSM_BG_RUNS: 0 off, 1 (default) by the share, 2 always, 3 always with an
+  // empty map (the read's overhead alone, profiles/background_runs/speed.md).
+  csmh::DevBuf bg_map, bg_info;
+  bool bg_ok = false;
+  int bg_runs = 1;
+  double bg_share = 0.0;  // set bits / corners of the current grid(s)
+  // ... and the phase kernel's map of 5 x 5 boxes, built with it
+  csmh::DevBuf bg_map5;
+  bool bg5_ok = false;
+  double bg5_share = 0.0;
   bool box_kernel = true;     // v6 box kernel for one-cell window steps; any CSM_KERNEL other
                               // than v6 turns it off (CSM_KERNEL=v4: the LDS-DMA row kernel)
   // Few-window launches (run_windows_small): the split kernel's slab and

@@ -207,6 +207,19 @@ struct LevelWork {
   // the largest n_used of the level's windows (0: unknown); the pair kernel
   // takes its run-free form at or below kPairNoRunBeams (csm_box.hip)
   int32_t max_n_used;
+  // The map of uniform boxes (score_box_pair_kernel; csm_palette.hip bg_geom):
+  // bit (ix0, iy0) set when the whole kPalMaxSpace^2 box from that padded
+  // corner holds the grid's background index, which bg_info names per grid of
+  // the stack (kBgInfoBg). Such a beam adds the same value to every candidate:
+  // the kernel counts it and never reads its box. bg_map = nullptr: unused.
+  const uint8_t* bg_map;
+  // ... and the same for the phase kernel's 5 x 5 boxes (score_phase_kernel's
+  // strip form, whose padded coordinates are the pair strips': kIStripPadLo =
+  // kStripPadLo); it reads pal_vals for the background's value too
+  const uint8_t* bg_map5;
+  const int32_t* bg_info;
+  int32_t bg_tiles8;      // bytes per row of 8 x 8 tiles
+  int32_t bg_grid_bytes;  // bytes per grid of the stack
 };
 
 // Argmax partial: best score of a block and its flat candidate index.
@@ -458,6 +471,28 @@ StripGeom strip_geom(int size_x, int size_y);
 hipError_t launch_build_strips(const uint8_t* idx, int pitch, int size_x, int size_y, int64_t idx_stride,
                                int n_grids, uint8_t* out, hipStream_t stream);
 bool box_pair_supported(int ns);
+// The pair kernel's map of uniform boxes. A scan-match grid is mostly one
+// value (the unknown value everywhere but the blurred wall bands); a beam
+// whose whole box holds it adds count * value to every candidate alike. The
+// background is the palette index covering the most in-grid cells; the map
+// holds one bit per padded box corner (counted from -kStripPadLo like the
+// pair kernel's box test), set when all kPalMaxSpace^2 cells from the corner
+// hold it in the padded image the strips are made from. Bits lie in 8 x 8
+// tiles, one 64-bit word each, byte iy0 & 7 of the word holding row iy0's
+// eight corners: a chunk's beams walk along a wall and share words and lines.
+struct BgGeom {
+  int32_t tiles_x, tiles_y;
+  int64_t grid_bytes;
+};
+BgGeom bg_geom(int size_x, int size_y);
+// info: kBgInfoInts ints per grid, zeroed by the launcher: the histogram of
+// the in-grid cells' indices, then the background index and the set bits.
+// out: the kPalMaxSpace^2 map (kBgInfoSet counts its bits); out5: the map of
+// kBgPhaseBox^2 boxes, the phase kernel's (kBgInfoSet5).
+constexpr int kBgInfoInts = 32, kBgInfoBg = 16, kBgInfoSet = 17, kBgInfoSet5 = 18;
+constexpr int kBgPhaseBox = 5;
+hipError_t launch_build_bg_map(const uint8_t* idx, int pitch, int size_x, int size_y, int64_t idx_stride,
+                               int n_grids, int32_t* info, uint8_t* out, uint8_t* out5, hipStream_t stream);
 // Strip copies of gridi for the phase kernel: copy c (of kIStripCopies) holds
 // cell x of row y at cell x + 4c of its strip row, strips kIStripCells cells
 // (32 bytes) wide with their rows contiguous, so a 5 x 5 phase box (corner

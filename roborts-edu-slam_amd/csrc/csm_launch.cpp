@@ -600,6 +600,9 @@ int Launch::decide() {
   const int64_t tile_n = (D.n_space + 15) / 16;
   F.tiled_ok = c->box_kernel && f == 1.0 && pad_ok && (int64_t)nw * tile_n * tile_n * D.n_angles <= INT32_MAX;
   if (dec.phase && c->phase_strips && (st = ensure_istrips(c)) != CSM_OK) return st;
+  // the phase kernel's map of uniform boxes is made from the palette's index grid
+  if (dec.phase && c->phase_strips && c->pair_kernel && c->bg_runs != 0 && (st = ensure_palette(c)) != CSM_OK)
+    return st;
   shape = launch_shape(dec, D.n_angles, D.n_space, F);
   if (shape.bps * nr() > INT32_MAX) return c->fail(CSM_ERR_UNSUPPORTED, "window too large for one launch");
   stride = score_stride(c, D, mode);
@@ -633,6 +636,13 @@ int Launch::level_work(const std::vector<int64_t>& pt_offsets, const std::vector
     L.strip_bytes = (int32_t)SG.strip_bytes;
     L.strip_copy_bytes = (int32_t)SG.copy_bytes;
     L.strip_grid_bytes = SG.grid_bytes;
+    if (c->bg_ok) {
+      const csm::BgGeom BG = csm::bg_geom(c->info.size_x, c->info.size_y);
+      L.bg_map = (const uint8_t*)c->bg_map.p;
+      L.bg_info = (const int32_t*)c->bg_info.p;
+      L.bg_tiles8 = BG.tiles_x * 8;
+      L.bg_grid_bytes = (int32_t)BG.grid_bytes;
+    }
   }
   if (shape.kernel == ScoreKernel::kPhase && c->phase_strips && c->istrips_ok) {
     const csm::StripGeom SG = csm::istrip_geom(c->info.size_x, c->info.size_y);
@@ -640,6 +650,14 @@ int Launch::level_work(const std::vector<int64_t>& pt_offsets, const std::vector
     L.istrip_bytes = (int32_t)SG.strip_bytes;
     L.istrip_copy_bytes = (int32_t)SG.copy_bytes;
     L.istrip_grid_bytes = SG.grid_bytes;
+    if (c->pair_kernel && c->bg_runs != 0 && c->bg5_ok && c->pal_gen == c->grid_gen && c->pal_src == c->d_gridi) {
+      const csm::BgGeom BG = csm::bg_geom(c->info.size_x, c->info.size_y);
+      L.bg_map5 = (const uint8_t*)c->bg_map5.p;
+      L.bg_info = (const int32_t*)c->bg_info.p;
+      L.bg_tiles8 = BG.tiles_x * 8;
+      L.bg_grid_bytes = (int32_t)BG.grid_bytes;
+      L.pal_vals = (const int32_t*)c->pal_vals.p;
+    }
   }
   L.n_cols = (int32_t)shape.n_cols;
   L.ktiles = shape.ktiles;

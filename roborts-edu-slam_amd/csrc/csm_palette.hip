@@ -19,6 +19,10 @@
 //                       copies the v11 pair box kernel reads
 //   istrips_kernel      the strip copies of gridi itself that the phase
 //                       kernel reads (8-cell strips, two copies)
+//   bg_hist_kernel,     (with the strips) the background index, the one most
+//   bg_map_kernel       in-grid cells hold, and the map of box corners whose
+//                       whole 13 x 13 box holds it, which the pair kernel
+//                       reads to skip such beams
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -163,6 +167,90 @@ __global__ __launch_bounds__(256) void pal_index_kernel(const int4* __restrict__
   }
 }
 
+// The padded index image the pair kernel reads, at grid cell (x, y) of either
+// sign: cells off the grid are index 0 but for column -1 and row -1, which
+// repeat column 0 and row 0 (kStripPadLo). The strip copies and the map of
+// uniform boxes are both made from it.
+__device__ __forceinline__ uint32_t padded_index(const uint8_t* __restrict__ idx, int pitch, int sx, int sy, int x,
+                                                 int y) {
+  return (y >= -1 && y < sy && x >= -1 && x < sx) ? idx[(int64_t)max(y, 0) * pitch + max(x, 0)] : 0u;
+}
+
+// Histogram of the in-grid cells' palette indices (palettes of at most
+// kPairMaxPal values), per grid of the stack (blockIdx.y).
+__global__ __launch_bounds__(256) void bg_hist_kernel(const uint8_t* __restrict__ idx, int pitch, int sx, int sy,
+                                                      int64_t idx_stride, int32_t* __restrict__ info) {
+  __shared__ uint32_t h[kPairMaxPal];
+  if (threadIdx.x < kPairMaxPal) h[threadIdx.x] = 0;
+  __syncthreads();
+  const uint8_t* g = idx + (int64_t)blockIdx.y * idx_stride;
+  const int64_t n = (int64_t)sx * sy;
+  uint32_t mine[kPairMaxPal] = {};
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const int y = (int)(i / sx), x = (int)(i - (int64_t)y * sx);
+    const uint32_t v = g[(int64_t)y * pitch + x] & (kPairMaxPal - 1);
+#pragma unroll
+    for (int k = 0; k < kPairMaxPal; ++k) mine[k] += v == (uint32_t)k;
+  }
+#pragma unroll
+  for (int k = 0; k < kPairMaxPal; ++k)
+    if (mine[k]) atomicAdd(&h[k], mine[k]);
+  __syncthreads();
+  if (threadIdx.x < kPairMaxPal && h[threadIdx.x])
+    atomicAdd(reinterpret_cast<uint32_t*>(info) + (int64_t)blockIdx.y * kBgInfoInts + threadIdx.x, h[threadIdx.x]);
+}
+
+// The map of uniform boxes (csm_internal.hpp BgGeom): one thread per 8 x 8
+// tile of padded corners. The background is the index with the largest count
+// (the lowest of equal ones). Row r of the tile's (N + 7)^2 cells gives the
+// eight corners' "N cells from here are background" bits; corner row j's byte
+// is the AND of rows j .. j + N - 1.
+template <int N>
+__global__ __launch_bounds__(256) void bg_map_kernel(const uint8_t* __restrict__ idx, int pitch, int sx, int sy,
+                                                     int64_t idx_stride, int tiles_x, int tiles_y,
+                                                     int32_t* __restrict__ info, int set_at,
+                                                     uint64_t* __restrict__ out) {
+  static_assert(N >= 2 && N + 7 <= 32, "a tile row's cells in one 32-bit mask");
+  int32_t* gi = info + (int64_t)blockIdx.y * kBgInfoInts;
+  uint32_t bg = 0, best = 0;
+  for (int k = 0; k < kPairMaxPal; ++k) {
+    const uint32_t c = (uint32_t)gi[k];
+    if (c > best) {
+      best = c;
+      bg = (uint32_t)k;
+    }
+  }
+  const uint8_t* g = idx + (int64_t)blockIdx.y * idx_stride;
+  const int64_t tiles = (int64_t)tiles_x * tiles_y;
+  uint32_t nset = 0;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < tiles; i += (int64_t)gridDim.x * 256) {
+    const int ty = (int)(i / tiles_x), tx = (int)(i - (int64_t)ty * tiles_x);
+    const int x0 = 8 * tx - kStripPadLo, y0 = 8 * ty - kStripPadLo;
+    uint32_t row[N + 7];
+#pragma unroll
+    for (int r = 0; r < N + 7; ++r) {
+      uint32_t m = 0;
+      for (int b = 0; b < N + 7; ++b) m |= (uint32_t)(padded_index(g, pitch, sx, sy, x0 + b, y0 + r) == bg) << b;
+      uint32_t a = m;  // bit b: cells b .. b + N - 1 of the row are background
+#pragma unroll
+      for (int s = 1; s < N; ++s) a &= m >> s;
+      row[r] = a & 0xFFu;
+    }
+    uint64_t w = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      uint32_t a = row[j];
+#pragma unroll
+      for (int r = 1; r < N; ++r) a &= row[j + r];
+      w |= (uint64_t)a << (8 * j);
+    }
+    out[(int64_t)blockIdx.y * tiles + i] = w;
+    nset += (uint32_t)__popcll(w);
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) gi[kBgInfoBg] = (int32_t)bg;
+  if (nset) atomicAdd(reinterpret_cast<uint32_t*>(gi) + set_at, nset);
+}
+
 // Strip copies of the palette index grid (v11 pair box kernel): copy c holds
 // cell x of row y at byte (x + kStripPadLo + kStripShift c) of its strip row,
 // strips kStripW bytes wide with their rows contiguous (row y of strip t at
@@ -181,15 +269,11 @@ __global__ __launch_bounds__(256) void pal_strips_kernel(const uint8_t* __restri
     const int64_t sr = r - (int64_t)c * per_copy;
     const int t = (int)(sr / rows);
     const int y = (int)(sr - (int64_t)t * rows) - kStripPadLo;
-    const uint8_t* src = idx + g * idx_stride + (int64_t)max(y, 0) * pitch;
     uint32_t w[4] = {0u, 0u, 0u, 0u};
-    if (y >= -1 && y < sy) {
 #pragma unroll
-      for (int b = 0; b < 16; ++b) {
-        const int x = kStripW * t + b - kStripShift * c - kStripPadLo;
-        const uint32_t v = (x >= -1 && x < sx) ? src[max(x, 0)] : 0u;
-        w[b >> 2] |= v << (8 * (b & 3));
-      }
+    for (int b = 0; b < 16; ++b) {
+      const int x = kStripW * t + b - kStripShift * c - kStripPadLo;
+      w[b >> 2] |= padded_index(idx + g * idx_stride, pitch, sx, sy, x, y) << (8 * (b & 3));
     }
     out[(g * grid_bytes + (int64_t)c * per_copy * kStripW) / 16 + sr] = make_uint4(w[0], w[1], w[2], w[3]);
   }
@@ -270,6 +354,36 @@ hipError_t launch_build_strips(const uint8_t* idx, int pitch, int size_x, int si
   const int64_t blocks = (total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192;
   hipLaunchKernelGGL(pal_strips_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, idx, pitch, size_x, size_y,
                      G.rows, G.n_strips, idx_stride, G.grid_bytes, n_grids, reinterpret_cast<uint4*>(out));
+  return hipGetLastError();
+}
+
+BgGeom bg_geom(int size_x, int size_y) {
+  BgGeom G{};
+  // corners 0 .. kStripPadLo + size - 1 per axis (the box test's in-grid range)
+  G.tiles_x = (kStripPadLo + size_x + 7) / 8;
+  G.tiles_y = (kStripPadLo + size_y + 7) / 8;
+  G.grid_bytes = (int64_t)G.tiles_x * G.tiles_y * 8;
+  return G;
+}
+
+hipError_t launch_build_bg_map(const uint8_t* idx, int pitch, int size_x, int size_y, int64_t idx_stride,
+                               int n_grids, int32_t* info, uint8_t* out, uint8_t* out5, hipStream_t stream) {
+  static_assert(kIStripPadLo == kStripPadLo, "one padded coordinate system for both maps");
+  const BgGeom G = bg_geom(size_x, size_y);
+  if (!idx || !info || !out || !out5 || n_grids < 1 || n_grids > 65535 || pitch < size_x) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(info, 0, (size_t)n_grids * kBgInfoInts * sizeof(int32_t), stream);
+  if (e != hipSuccess) return e;
+  const int64_t cells = (int64_t)size_x * size_y, tiles = (int64_t)G.tiles_x * G.tiles_y;
+  const int64_t hb = (cells + 4095) / 4096 < 1024 ? (cells + 4095) / 4096 : 1024;
+  hipLaunchKernelGGL(bg_hist_kernel, dim3((unsigned)hb, (unsigned)n_grids), dim3(256), 0, stream, idx, pitch, size_x,
+                     size_y, idx_stride, info);
+  const int64_t mb = (tiles + 255) / 256 < 4096 ? (tiles + 255) / 256 : 4096;
+  hipLaunchKernelGGL(bg_map_kernel<kPalMaxSpace>, dim3((unsigned)mb, (unsigned)n_grids), dim3(256), 0, stream, idx,
+                     pitch, size_x, size_y, idx_stride, G.tiles_x, G.tiles_y, info, kBgInfoSet,
+                     reinterpret_cast<uint64_t*>(out));
+  hipLaunchKernelGGL(bg_map_kernel<kBgPhaseBox>, dim3((unsigned)mb, (unsigned)n_grids), dim3(256), 0, stream, idx,
+                     pitch, size_x, size_y, idx_stride, G.tiles_x, G.tiles_y, info, kBgInfoSet5,
+                     reinterpret_cast<uint64_t*>(out5));
   return hipGetLastError();
 }
 

@@ -79,7 +79,13 @@ typedef int32_t v4i __attribute__((ext_vector_type(4)));
 // would otherwise load and classify seven dead chunks per wave.
 constexpr int kPhaseShortBeams = 128;
 
-template <int NS, int C, int NQ, bool BEST, bool ST, int KCH = kChunks>
+// BG (strip form): the grid has a map of box corners whose whole C x C box
+// holds the background value V (L.bg_map5, csm_internal.hpp BgGeom; the strips'
+// padded coordinates are the map's). Such a beam adds V to every candidate
+// whatever its buckets: it gets no pair, is counted, and count * V joins every
+// candidate's sum once. The map's bytes of a segment's chunks are all asked
+// for before the first is read.
+template <int NS, int C, int NQ, bool BEST, bool ST, int KCH = kChunks, bool BG = false>
 __global__ __launch_bounds__(64, CSM_PHASE_WAVES) void score_phase_kernel(LevelWork L, PhaseTable T,
                                                          const ScanWork* __restrict__ scans,
                                                          const double2* __restrict__ pts,
@@ -160,7 +166,10 @@ __global__ __launch_bounds__(64, CSM_PHASE_WAVES) void score_phase_kernel(LevelW
   };
   // Beam cb + lane (live below lim): its box offset and pair (pair < 0: it adds
   // nothing here — not live, box wholly past the grid's high edges, or rejected).
-  auto classify = [&](const double2 p, int cb, int lim, double& lx, double& ly, bool& rejected) -> int2 {
+  // (bgat, BG: the byte of the map that holds the corner's bit, 0 without a
+  // pair; the bit, ix0 & 7, rides above the pair: pair | bit << 8)
+  auto classify = [&](const double2 p, int cb, int lim, double& lx, double& ly, bool& rejected,
+                      uint32_t* bgat = nullptr) -> int2 {
     lx = ae.cosine * p.x - ae.sine * p.y;  // :179
     ly = ae.sine * p.x + ae.cosine * p.y;  // :180
     const double tx = (lx + x_0) + (0.5 + kPad);  // (a shift by kPad within 2^-28 cells)
@@ -200,6 +209,10 @@ __global__ __launch_bounds__(64, CSM_PHASE_WAVES) void score_phase_kernel(LevelW
     } else {
       o = iy0 * pitch4 + ix0 * 4;
     }
+    if constexpr (BG) {
+      if (bgat) *bgat = use ? (uint32_t)((iy0 >> 3) * L.bg_tiles8 + (ix0 & ~7) + (iy0 & 7)) : 0u;
+      return make_int2(use ? o : 0, use ? (qx * NQ + qy) | ((ix0 & 7) << 8) : -1);
+    }
     return make_int2(use ? o : 0, use ? qx * NQ + qy : -1);
   };
   auto point = [&](int b) { return P[(int64_t)min(b, n_used - 1) * step]; };
@@ -227,6 +240,12 @@ __global__ __launch_bounds__(64, CSM_PHASE_WAVES) void score_phase_kernel(LevelW
   for (int r = 0; r < R; ++r) sum[r] = 0;
   const int lane_cell = cv * C + 4 * ch;  // this lane's first box cell in a pair's sums
 
+  static_assert(!BG || (ST && C == kBgPhaseBox), "the map is the strip form's, of C x C boxes");
+  const __amdgpu_buffer_rsrc_t bgmap = dev::uniform_rsrc(
+      BG ? L.bg_map5 + (int64_t)S.grid_index * L.bg_grid_bytes : nullptr, BG ? L.bg_grid_bytes : 0);
+  int64_t bg_val = 0;
+  int nbg = 0;  // beams dropped for the background (wave-uniform)
+  if constexpr (BG) bg_val = L.pal_vals[L.bg_info[S.grid_index * kBgInfoInts + kBgInfoBg] & (kPairMaxPal - 1)];
   uint64_t slow = 0;  // bit c: 64-beam chunk c holds a rejected beam (bit 63: some chunk >= 63)
   static_assert(KCH >= 1 && KCH <= kChunks, "segments of at most kSeg beams");
   for (int s0 = 0; s0 < n_used; s0 += 64 * KCH) {
@@ -239,16 +258,30 @@ __global__ __launch_bounds__(64, CSM_PHASE_WAVES) void score_phase_kernel(LevelW
     if (lane < NP) cursor[lane] = 0;
     __syncthreads();
     int offr[KCH], pairr[KCH];
+    uint8_t bgb[BG ? KCH : 1];
 #pragma unroll
     for (int u = 0; u < KCH; ++u) {
       const int cb = s0 + 64 * u;
       double lx, ly;
       bool rej;
-      const int2 c = classify(pq[u], cb, s1, lx, ly, rej);
+      uint32_t at = 0;
+      const int2 c = classify(pq[u], cb, s1, lx, ly, rej, &at);
       slow |= (uint64_t)(__builtin_amdgcn_ballot_w64(rej) != 0) << min(cb >> 6, 63);
       offr[u] = c.x;
       pairr[u] = c.y;
-      if (c.y >= 0) atomicAdd(&cursor[c.y], 1);
+      if constexpr (BG)
+        bgb[u] = __builtin_amdgcn_raw_buffer_load_b8(bgmap, (int)at, 0, 0);
+      else if (c.y >= 0)
+        atomicAdd(&cursor[c.y], 1);
+    }
+    if constexpr (BG) {
+#pragma unroll
+      for (int u = 0; u < KCH; ++u) {
+        const bool drop = pairr[u] >= 0 && (((uint32_t)bgb[u] >> (pairr[u] >> 8)) & 1u) != 0;
+        nbg += __builtin_popcountll(__builtin_amdgcn_ballot_w64(drop));
+        pairr[u] = (drop || pairr[u] < 0) ? -1 : (pairr[u] & 0xFF);
+        if (pairr[u] >= 0) atomicAdd(&cursor[pairr[u]], 1);
+      }
     }
     __syncthreads();
     // 1b. lists: pair p gets whole groups of SL beams, its groups split into
@@ -355,6 +388,10 @@ __global__ __launch_bounds__(64, CSM_PHASE_WAVES) void score_phase_kernel(LevelW
       sum[r] += psum[pr * PC + v * C + u];
     }
   }
+  if constexpr (BG) {  // the dropped beams' share, the same for every candidate
+#pragma unroll
+    for (int r = 0; r < R; ++r) sum[r] += (int64_t)nbg * bg_val;
+  }
 
   // rejected beams, cell by cell with the reference's expressions, four beams
   // at a time (their gathers issued together)
@@ -414,12 +451,15 @@ __global__ __launch_bounds__(64, CSM_PHASE_WAVES) void score_phase_kernel(LevelW
 template <int NS, int C, int NQ, bool ST, int KCH>
 hipError_t launch_phase_k(const LevelWork& L, const PhaseTable& T, const ScanWork* s, const double2* p,
                           const AngleEntry* an, double* out, BestPartial* part, unsigned nblk, hipStream_t stream) {
-  if (part)
-    hipLaunchKernelGGL((score_phase_kernel<NS, C, NQ, true, ST, KCH>), dim3(nblk), dim3(64), 0, stream, L, T, s, p,
-                       an, out, part);
-  else
-    hipLaunchKernelGGL((score_phase_kernel<NS, C, NQ, false, ST, KCH>), dim3(nblk), dim3(64), 0, stream, L, T, s, p,
-                       an, out, part);
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(nblk), dim3(64), 0, stream, L, T, s, p, an, out, part); };
+  if constexpr (ST) {
+    if (L.bg_map5) {  // the map of uniform boxes
+      part ? go(score_phase_kernel<NS, C, NQ, true, ST, KCH, true>)
+           : go(score_phase_kernel<NS, C, NQ, false, ST, KCH, true>);
+      return hipGetLastError();
+    }
+  }
+  part ? go(score_phase_kernel<NS, C, NQ, true, ST, KCH>) : go(score_phase_kernel<NS, C, NQ, false, ST, KCH>);
   return hipGetLastError();
 }
 
@@ -455,6 +495,11 @@ hipError_t launch_score_phase(const LevelWork& L, const PhaseTable& T, const Sca
     if (L.istrip_bytes != G.strip_bytes || L.istrip_copy_bytes != G.copy_bytes || L.istrip_grid_bytes != G.grid_bytes ||
         G.grid_bytes > INT32_MAX)
       return hipErrorInvalidValue;
+    if (L.bg_map5) {  // the map's geometry is this grid's
+      const BgGeom BG = bg_geom(L.size_x, L.size_y);
+      if (!L.bg_info || !L.pal_vals || L.bg_tiles8 != BG.tiles_x * 8 || L.bg_grid_bytes != BG.grid_bytes)
+        return hipErrorInvalidValue;
+    }
     return launch_phase<11, 5, 5, true>(L, T, d_scans, p, d_angles, d_out, d_partials, (unsigned)nblk, stream);
   }
   return launch_phase<11, 5, 5, false>(L, T, d_scans, p, d_angles, d_out, d_partials, (unsigned)nblk, stream);
