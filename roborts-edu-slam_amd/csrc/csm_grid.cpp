@@ -2,8 +2,8 @@
 // points): the reference's AoS ProbabilityCell map uploaded and kept keyed on
 // (cells pointer, stride, size, map_update_index) (grid_map_cell.h:301-328,
 // grid_map_base.h:352-354), incremental row / cell refreshes, grid stacks,
-// borrowed device maps (csm_gridmap), and the exact fixed-point copy every
-// integer-mode kernel reads.
+// borrowed device maps (csm_gridmap), the exact fixed-point copy every
+// integer-mode kernel reads, and the copies made of it (csm_grid_copies.hpp).
 #include "csm_host.hpp"
 
 namespace csmh {
@@ -129,6 +129,15 @@ struct PackStats {
   int min_g = INT32_MAX;
   float max_abs = 0.f;
   bool nonfinite = false;
+  void add(float v) {
+    bool z;
+    merge({float_granularity(v, &z), std::fabs(v), !std::isfinite(v)});
+  }
+  void merge(const PackStats& p) {
+    min_g = std::min(min_g, p.min_g);
+    max_abs = std::max(max_abs, p.max_abs);
+    nonfinite = nonfinite || p.nonfinite;
+  }
 };
 PackStats pack_rows(csm_ctx* c, const void* cells, int64_t stride, int32_t sx, int32_t y0, int32_t y1, float* dst) {
   const int rows = y1 - y0;
@@ -145,22 +154,12 @@ PackStats pack_rows(csm_ctx* c, const void* cells, int64_t stride, int32_t sx, i
       } else {
         for (int32_t x = 0; x < sx; ++x) std::memcpy(out + x, src + (int64_t)x * stride, 4);
       }
-      for (int32_t x = 0; x < sx; ++x) {
-        const float v = out[x];
-        if (!std::isfinite(v)) ps.nonfinite = true;
-        bool z;
-        ps.min_g = std::min(ps.min_g, float_granularity(v, &z));
-        ps.max_abs = std::max(ps.max_abs, std::fabs(v));
-      }
+      for (int32_t x = 0; x < sx; ++x) ps.add(out[x]);
     }
     part[(size_t)t] = ps;
   });
   PackStats all;
-  for (const auto& p : part) {
-    all.min_g = std::min(all.min_g, p.min_g);
-    all.max_abs = std::max(all.max_abs, p.max_abs);
-    all.nonfinite = all.nonfinite || p.nonfinite;
-  }
+  for (const auto& p : part) all.merge(p);
   return all;
 }
 
@@ -178,126 +177,160 @@ void note_new_values(csm_ctx* c, const PackStats& ps) {
   c->int_max_abs = std::max(c->int_max_abs, (double)ps.max_abs);
 }
 
-// The share of set bits in the map of uniform boxes below which the pair
-// kernel does not read it. The read costs the same whatever it finds: with an
-// empty map forced on, the headline step is 0.060 ms longer; with config 2's
-// map (38 % of corners set) it is 0.149 ms shorter than that. Taking the gain
-// as proportional to the share, the two meet at 0.38 * 0.060 / 0.149 = 0.15
-// (profiles/background_runs/speed.md).
-constexpr double kBgMinShare = 0.16;
+static_assert(kStripsMaxPal == csm::kPairMaxPal, "the rule's palette bound is the pair kernel's");
 
 // The palette copy of the current gridi (csm_palette.hip), built once per
 // grid generation: the grid's distinct fixed-point values and a byte per cell
 // holding its value's index, read by the v10 palette box kernel. A grid with
 // more than csm::kPalMax values gets none (pal_n = 0).
-int ensure_palette(csm_ctx* c) {
+static int ensure_palette(csm_ctx* c) {
+  GridCopies& G = c->copies;
   if (!c->int_ok || !c->d_gridi) {
-    c->pal_n = 0;
+    G.pal_n = 0;
     return CSM_OK;
   }
-  if (c->pal_gen == c->grid_gen && c->pal_src == c->d_gridi) return CSM_OK;
-  const int64_t n = (int64_t)c->pitch * (c->info.size_y + csm::kGridiPadRows) * c->n_grids;
+  if (G.pal_key.current(c->grid_gen, c->d_gridi)) return CSM_OK;
+  const int64_t idx_stride = c->gridi_cells(), n = idx_stride * c->n_grids;
   hipError_t e;
-  if ((e = c->pal_grid.ensure((size_t)n)) != hipSuccess) return c->hip_fail(e, "hipMalloc(palette grid)");
-  if ((e = c->pal_vals.ensure((csm::kPalMax + 4) * sizeof(int32_t))) != hipSuccess)
+  if ((e = G.pal_grid.ensure((size_t)n)) != hipSuccess) return c->hip_fail(e, "hipMalloc(palette grid)");
+  if ((e = G.pal_vals.ensure((csm::kPalMax + 4) * sizeof(int32_t))) != hipSuccess)
     return c->hip_fail(e, "hipMalloc(palette)");
-  if ((e = c->pal_scratch.ensure((size_t)csm::pal_scratch_ints(n) * sizeof(int32_t))) != hipSuccess)
+  if ((e = G.pal_scratch.ensure((size_t)csm::pal_scratch_ints(n) * sizeof(int32_t))) != hipSuccess)
     return c->hip_fail(e, "hipMalloc(palette scratch)");
-  int32_t* vals = (int32_t*)c->pal_vals.p;
-  if ((e = csm::launch_build_palette(c->d_gridi, n, (int32_t*)c->pal_scratch.p, vals, vals + csm::kPalMax,
-                                     (uint8_t*)c->pal_grid.p, c->stream)) != hipSuccess)
+  int32_t* vals = (int32_t*)G.pal_vals.p;
+  if ((e = csm::launch_build_palette(c->d_gridi, n, (int32_t*)G.pal_scratch.p, vals, vals + csm::kPalMax,
+                                     (uint8_t*)G.pal_grid.p, c->stream)) != hipSuccess)
     return c->hip_fail(e, "palette kernels");
   int32_t m = 0;
   if ((e = hipMemcpyAsync(&m, vals + csm::kPalMax, sizeof(m), hipMemcpyDeviceToHost, c->stream)) != hipSuccess ||
       (e = hipStreamSynchronize(c->stream)) != hipSuccess)
     return c->hip_fail(e, "palette size");
-  c->pal_n = (m >= 1 && m <= csm::kPalMax) ? m : 0;
-  c->pal_strips_ok = false;
-  c->bg_ok = c->bg5_ok = false;
-  c->bg_share = c->bg5_share = 0.0;
+  G.pal_n = (m >= 1 && m <= csm::kPalMax) ? m : 0;
+  G.pal_strips_ok = false;
+  G.bg_ok = G.bg5_ok = false;
+  G.bg_share = G.bg5_share = 0.0;
   const csm::StripGeom SG = csm::strip_geom(c->info.size_x, c->info.size_y);
-  // (the pair kernel's strip offsets are 24-bit products: strips under 2^24 bytes)
-  if (c->pair_kernel && c->pal_n >= 1 && c->pal_n <= csm::kPairMaxPal && SG.grid_bytes <= INT32_MAX &&
-      SG.strip_bytes < (1 << 24)) {
-    if ((e = c->pal_strips.ensure((size_t)SG.grid_bytes * (size_t)c->n_grids)) != hipSuccess)
+  if (pal_strips_built(c->pair_kernel, G.pal_n, SG.grid_bytes, SG.strip_bytes)) {
+    if ((e = G.pal_strips.ensure((size_t)SG.grid_bytes * (size_t)c->n_grids)) != hipSuccess)
       return c->hip_fail(e, "hipMalloc(palette strips)");
-    const int64_t idx_stride = (int64_t)c->pitch * (c->info.size_y + csm::kGridiPadRows);
-    if ((e = csm::launch_build_strips((const uint8_t*)c->pal_grid.p, c->pitch, c->info.size_x, c->info.size_y,
-                                      idx_stride, c->n_grids, (uint8_t*)c->pal_strips.p, c->stream)) != hipSuccess)
+    if ((e = csm::launch_build_strips((const uint8_t*)G.pal_grid.p, c->pitch, c->info.size_x, c->info.size_y,
+                                      idx_stride, c->n_grids, (uint8_t*)G.pal_strips.p, c->stream)) != hipSuccess)
       return c->hip_fail(e, "pal_strips_kernel");
-    // the map of uniform boxes, from the same index grid (byte offsets and the
-    // corner's bit in one 32-bit key: maps under 2^28 bytes)
+    // the map of uniform boxes, from the same index grid
     const csm::BgGeom BG = csm::bg_geom(c->info.size_x, c->info.size_y);
-    const bool bg_build = c->bg_runs != 0 && BG.grid_bytes < (1 << 28) && c->n_grids <= 65535;
+    const bool bg_build = bg_maps_built(c->bg_runs, BG.grid_bytes, c->n_grids);
+    const size_t map_bytes = (size_t)BG.grid_bytes * (size_t)c->n_grids;
     std::vector<int32_t> bg_info((size_t)c->n_grids * csm::kBgInfoInts);
     if (bg_build) {
-      if ((e = c->bg_map.ensure((size_t)BG.grid_bytes * (size_t)c->n_grids)) != hipSuccess ||
-          (e = c->bg_map5.ensure((size_t)BG.grid_bytes * (size_t)c->n_grids)) != hipSuccess ||
-          (e = c->bg_info.ensure(bg_info.size() * sizeof(int32_t))) != hipSuccess)
+      if ((e = G.bg_map.ensure(map_bytes)) != hipSuccess || (e = G.bg_map5.ensure(map_bytes)) != hipSuccess ||
+          (e = G.bg_info.ensure(bg_info.size() * sizeof(int32_t))) != hipSuccess)
         return c->hip_fail(e, "hipMalloc(background map)");
-      if ((e = csm::launch_build_bg_map((const uint8_t*)c->pal_grid.p, c->pitch, c->info.size_x, c->info.size_y,
-                                        idx_stride, c->n_grids, (int32_t*)c->bg_info.p, (uint8_t*)c->bg_map.p,
-                                        (uint8_t*)c->bg_map5.p, c->stream)) != hipSuccess)
+      if ((e = csm::launch_build_bg_map((const uint8_t*)G.pal_grid.p, c->pitch, c->info.size_x, c->info.size_y,
+                                        idx_stride, c->n_grids, (int32_t*)G.bg_info.p, (uint8_t*)G.bg_map.p,
+                                        (uint8_t*)G.bg_map5.p, c->stream)) != hipSuccess)
         return c->hip_fail(e, "bg_map_kernel");
-      if (c->bg_runs == 3 &&
-          ((e = hipMemsetAsync(c->bg_map.p, 0, (size_t)BG.grid_bytes * (size_t)c->n_grids, c->stream)) != hipSuccess ||
-           (e = hipMemsetAsync(c->bg_map5.p, 0, (size_t)BG.grid_bytes * (size_t)c->n_grids, c->stream)) != hipSuccess))
+      if (c->bg_runs == 3 && ((e = hipMemsetAsync(G.bg_map.p, 0, map_bytes, c->stream)) != hipSuccess ||
+                              (e = hipMemsetAsync(G.bg_map5.p, 0, map_bytes, c->stream)) != hipSuccess))
         return c->hip_fail(e, "hipMemsetAsync(background map)");
-      if ((e = hipMemcpyAsync(bg_info.data(), c->bg_info.p, bg_info.size() * sizeof(int32_t), hipMemcpyDeviceToHost,
+      if ((e = hipMemcpyAsync(bg_info.data(), G.bg_info.p, bg_info.size() * sizeof(int32_t), hipMemcpyDeviceToHost,
                               c->stream)) != hipSuccess)
         return c->hip_fail(e, "hipMemcpyAsync(background map)");
     }
     // other parts' streams read the strips next (like gridi)
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hip_fail(e, "hipStreamSynchronize(strips)");
-    c->pal_strips_ok = true;
+    G.pal_strips_ok = true;
     if (bg_build) {
       double set = 0.0, set5 = 0.0;
       for (int gi = 0; gi < c->n_grids; ++gi) {
         set += (double)(uint32_t)bg_info[(size_t)gi * csm::kBgInfoInts + csm::kBgInfoSet];
         set5 += (double)(uint32_t)bg_info[(size_t)gi * csm::kBgInfoInts + csm::kBgInfoSet5];
       }
-      c->bg_share = set / ((double)BG.grid_bytes * 8.0 * c->n_grids);
-      c->bg5_share = set5 / ((double)BG.grid_bytes * 8.0 * c->n_grids);
-      c->bg_ok = c->bg_runs >= 2 || c->bg_share >= kBgMinShare;
-      c->bg5_ok = c->bg_runs >= 2 || c->bg5_share >= kBgMinShare;
+      G.bg_share = set / ((double)BG.grid_bytes * 8.0 * c->n_grids);
+      G.bg5_share = set5 / ((double)BG.grid_bytes * 8.0 * c->n_grids);
+      G.bg_ok = bg_map_used(c->bg_runs, G.bg_share);
+      G.bg5_ok = bg_map_used(c->bg_runs, G.bg5_share);
       if (c->profiling) {
         c->account("grid:bg_map", 0.f, (double)BG.grid_bytes * c->n_grids, set);
         c->account("grid:bg_map5", 0.f, (double)BG.grid_bytes * c->n_grids, set5);
       }
     }
   }
-  c->pal_gen = c->grid_gen;
-  c->pal_src = c->d_gridi;
-  if (c->profiling) c->account("grid:palette", 0.f, (double)n, (double)c->pal_n);
+  G.pal_key = {c->grid_gen, c->d_gridi};
+  if (c->profiling) c->account("grid:palette", 0.f, (double)n, (double)G.pal_n);
   return CSM_OK;
 }
 
 // The strip copies of the current gridi for the phase kernel, once per grid
 // generation (istrips_ok = false: none, the kernel reads gridi row-major).
-int ensure_istrips(csm_ctx* c) {
+static int ensure_istrips(csm_ctx* c) {
+  GridCopies& G = c->copies;
   if (!c->int_ok || !c->d_gridi) {
-    c->istrips_ok = false;
+    G.istrips_ok = false;
     return CSM_OK;
   }
-  if (c->istrips_gen == c->grid_gen && c->istrips_src == c->d_gridi) return CSM_OK;
-  c->istrips_ok = false;
+  if (G.istrips_key.current(c->grid_gen, c->d_gridi)) return CSM_OK;
+  G.istrips_ok = false;
   const csm::StripGeom SG = csm::istrip_geom(c->info.size_x, c->info.size_y);
-  if (SG.grid_bytes <= INT32_MAX) {
+  if (istrips_built(SG.grid_bytes)) {
     hipError_t e;
-    if ((e = c->istrips.ensure((size_t)SG.grid_bytes * (size_t)c->n_grids)) != hipSuccess)
+    if ((e = G.istrips.ensure((size_t)SG.grid_bytes * (size_t)c->n_grids)) != hipSuccess)
       return c->hip_fail(e, "hipMalloc(gridi strips)");
-    const int64_t stride = (int64_t)c->pitch * (c->info.size_y + csm::kGridiPadRows);
-    if ((e = csm::launch_build_istrips(c->d_gridi, c->pitch, c->info.size_x, c->info.size_y, stride, c->n_grids,
-                                       (int32_t*)c->istrips.p, c->stream)) != hipSuccess)
+    if ((e = csm::launch_build_istrips(c->d_gridi, c->pitch, c->info.size_x, c->info.size_y, c->gridi_cells(),
+                                       c->n_grids, (int32_t*)G.istrips.p, c->stream)) != hipSuccess)
       return c->hip_fail(e, "istrips_kernel");
     // other parts' streams read the strips next (like gridi)
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hip_fail(e, "hipStreamSynchronize(istrips)");
-    c->istrips_ok = true;
+    G.istrips_ok = true;
     if (c->profiling) c->account("grid:istrips", 0.f, (double)SG.grid_bytes * c->n_grids, 0.0);
   }
-  c->istrips_gen = c->grid_gen;
-  c->istrips_src = c->d_gridi;
+  G.istrips_key = {c->grid_gen, c->d_gridi};
   return CSM_OK;
+}
+
+int ensure_level_copies(csm_ctx* c, bool pair, bool phase) {
+  int st = CSM_OK;
+  if (pair) st = ensure_palette(c);
+  if (st == CSM_OK && phase && c->phase_strips) st = ensure_istrips(c);
+  if (st == CSM_OK && phase && phase_wants_palette(c->phase_strips, c->pair_kernel, c->bg_runs)) st = ensure_palette(c);
+  return st;
+}
+
+// The pair kernel's palette strips and the phase kernel's strips of gridi,
+// each with its map of uniform boxes where that is used (the phase kernel's:
+// and of the current grid, a phase level does not always build the palette).
+void level_work_copies(const csm_ctx* c, ScoreKernel kernel, LevelWork& L) {
+  const GridCopies& G = c->copies;
+  const auto bg_fields = [&](const uint8_t*& map, const DevBuf& buf) {  // either map and what it is read with
+    const csm::BgGeom BG = csm::bg_geom(c->info.size_x, c->info.size_y);
+    map = (const uint8_t*)buf.p;
+    L.bg_info = (const int32_t*)G.bg_info.p;
+    L.bg_tiles8 = BG.tiles_x * 8;
+    L.bg_grid_bytes = (int32_t)BG.grid_bytes;
+  };
+  if (kernel == ScoreKernel::kBoxPair) {
+    const csm::StripGeom SG = csm::strip_geom(c->info.size_x, c->info.size_y);
+    L.pal_n = G.pal_n;
+    L.pal_grid = (const uint8_t*)G.pal_grid.p;
+    L.pal_vals = (const int32_t*)G.pal_vals.p;
+    L.pal_stride = c->gridi_cells();
+    L.pal_strips = (const uint8_t*)G.pal_strips.p;
+    L.strip_bytes = (int32_t)SG.strip_bytes;
+    L.strip_copy_bytes = (int32_t)SG.copy_bytes;
+    L.strip_grid_bytes = SG.grid_bytes;
+    if (G.bg_ok) bg_fields(L.bg_map, G.bg_map);
+  }
+  if (kernel == ScoreKernel::kPhase && c->phase_strips && G.istrips_ok) {
+    const csm::StripGeom SG = csm::istrip_geom(c->info.size_x, c->info.size_y);
+    L.istrips = (const int32_t*)G.istrips.p;
+    L.istrip_bytes = (int32_t)SG.strip_bytes;
+    L.istrip_copy_bytes = (int32_t)SG.copy_bytes;
+    L.istrip_grid_bytes = SG.grid_bytes;
+    if (phase_wants_palette(c->phase_strips, c->pair_kernel, c->bg_runs) && G.bg5_ok &&
+        G.pal_key.current(c->grid_gen, c->d_gridi)) {
+      bg_fields(L.bg_map5, G.bg_map5);
+      L.pal_vals = (const int32_t*)G.pal_vals.p;
+    }
+  }
 }
 
 }  // namespace csmh
@@ -308,14 +341,35 @@ extern "C" {
 
 namespace {
 
-int check_grid_args(csm_ctx* c, const void* cells, int64_t stride, const csm_map_info* info) {
-  if (info->size_x <= 0 || info->size_y <= 0 || !(info->resolution > 0.0))
-    return c->fail(CSM_ERR_INVALID_ARG, "grid size and resolution must be positive");
+// A grid's size and resolution, and the kernels' 2^31 cell limit.
+int check_grid_size(csm_ctx* c, const csm_map_info* info, const char* what = "grid size and resolution must be positive") {
+  if (info->size_x <= 0 || info->size_y <= 0 || !(info->resolution > 0.0)) return c->fail(CSM_ERR_INVALID_ARG, what);
   if ((int64_t)info->size_x * info->size_y >= ((int64_t)1 << 31))
     return c->fail(CSM_ERR_INVALID_ARG, "grid larger than 2^31 cells");
+  return CSM_OK;
+}
+
+int check_grid_args(csm_ctx* c, const void* cells, int64_t stride, const csm_map_info* info) {
+  if (const int st = check_grid_size(c, info)) return st;
   if (!cells || stride < 4 || stride % 4 != 0)
     return c->fail(CSM_ERR_INVALID_ARG, "cells must be non-null with a stride that is a multiple of 4 bytes");
   return CSM_OK;
+}
+
+// Make n_grids grids at `dev` the current grid, keyed on (cells, stride,
+// version, size); cells = nullptr: no host map's, never found again.
+void adopt_grid(csm_ctx* c, const float* dev, int32_t n_grids, const csm_map_info& info, const void* cells = nullptr,
+                int64_t stride = 0, int64_t version = -1) {
+  c->info = info;
+  c->d_grid = dev;
+  c->n_grids = n_grids;
+  c->has_grid = true;
+  c->int_checked = false;
+  c->key_cells = cells;
+  c->key_stride = stride;
+  c->key_version = version;
+  c->key_sx = info.size_x;
+  c->key_sy = info.size_y;
 }
 
 // Whole-grid upload into the current slot (selected by the caller): rows are
@@ -332,16 +386,7 @@ int upload_grid(csm_ctx* c, const void* cells, int64_t stride, const csm_map_inf
     return c->hip_fail(e, "hipMemcpyAsync(grid)");
   if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hip_fail(e, "hipStreamSynchronize(grid)");
   if (c->profiling) c->account("grid:upload", 0.f, (double)(ncell * sizeof(float)), 0.0);
-  c->info = *info;
-  c->d_grid = (const float*)c->grid_buf.p;
-  c->n_grids = 1;
-  c->has_grid = true;
-  c->int_checked = false;
-  c->key_cells = cells;
-  c->key_stride = stride;
-  c->key_version = version;
-  c->key_sx = info->size_x;
-  c->key_sy = info->size_y;
+  adopt_grid(c, (const float*)c->grid_buf.p, 1, *info, cells, stride, version);
   return CSM_OK;
 }
 
@@ -445,10 +490,7 @@ int csm_update_grid_cells(csm_ctx* c, const void* cells, int64_t stride, const c
       std::memcpy(&v, (const char*)cells + (int64_t)k * stride, 4);
       u[i].index = k;
       u[i].value = v;
-      if (!std::isfinite(v)) ps.nonfinite = true;
-      bool z;
-      ps.min_g = std::min(ps.min_g, float_granularity(v, &z));
-      ps.max_abs = std::max(ps.max_abs, std::fabs(v));
+      ps.add(v);
     }
     part[(size_t)t] = ps;
   });
@@ -458,11 +500,7 @@ int csm_update_grid_cells(csm_ctx* c, const void* cells, int64_t stride, const c
   c->key_version = version;
   if (n_indices == 0) return CSM_OK;
   PackStats all;
-  for (const auto& p : part) {
-    all.min_g = std::min(all.min_g, p.min_g);
-    all.max_abs = std::max(all.max_abs, p.max_abs);
-    all.nonfinite = all.nonfinite || p.nonfinite;
-  }
+  for (const auto& p : part) all.merge(p);
   note_new_values(c, all);
   const size_t bytes = (size_t)n_indices * sizeof(csm::CellUpdate);
   if ((e = c->d_updates.ensure(bytes)) != hipSuccess) return c->hip_fail(e, "hipMalloc(cell updates)");
@@ -483,19 +521,23 @@ int csm_update_grid_cells(csm_ctx* c, const void* cells, int64_t stride, const c
 }
 
 namespace {
+// A device map's geometry as a grid's info.
+csm_map_info view_info(const csm::GridMapView& v, int32_t update_index) {
+  csm_map_info info{};
+  info.resolution = v.resolution;
+  info.offset_x = v.offset_x;
+  info.offset_y = v.offset_y;
+  info.size_x = v.size_x;
+  info.size_y = v.size_y;
+  info.update_index = update_index;
+  return info;
+}
+
 int set_grid_device_locked(csm_ctx* c, const float* dev, const csm_map_info* info) {
-  if (!dev || info->size_x <= 0 || info->size_y <= 0 || !(info->resolution > 0.0))
-    return c->fail(CSM_ERR_INVALID_ARG, "invalid device grid");
-  if ((int64_t)info->size_x * info->size_y >= ((int64_t)1 << 31))
-    return c->fail(CSM_ERR_INVALID_ARG, "grid larger than 2^31 cells");
+  if (!dev) return c->fail(CSM_ERR_INVALID_ARG, "invalid device grid");
+  if (const int st = check_grid_size(c, info, "invalid device grid")) return st;
   park_current(c);
-  c->info = *info;
-  c->d_grid = dev;
-  c->n_grids = 1;
-  c->has_grid = true;
-  c->int_checked = false;
-  c->key_cells = nullptr;
-  c->key_version = -1;
+  adopt_grid(c, dev, 1, *info);
   return CSM_OK;
 }
 }  // namespace
@@ -535,13 +577,7 @@ int csm_set_grid_gridmap(csm_ctx* c, csm_gridmap* map) {
   if (c->reader_map != map) release_map_reader(c);
   csm::gridmap_add_reader(map, c->stream);
   c->reader_map = map;
-  csm_map_info info{};
-  info.resolution = v.resolution;
-  info.offset_x = v.offset_x;
-  info.offset_y = v.offset_y;
-  info.size_x = v.size_x;
-  info.size_y = v.size_y;
-  info.update_index = v.map_update_index;
+  const csm_map_info info = view_info(v, v.map_update_index);
   if ((st = set_grid_device_locked(c, v.prob, &info)) != CSM_OK) return st;
   if (fx.ok && fx.outside == c->outside) {  // ensure_int_grid's state, borrowed
     c->int_checked = true;
@@ -564,10 +600,8 @@ int csm_set_grid_stack(csm_ctx* c, const float* cells, int32_t n_grids, const cs
   DeviceGuard g(c->device);
   if (const int dst = pipe_drain(c)) return dst;  // a submitted batch still reads the context
   release_map_reader(c);
-  if (info->size_x <= 0 || info->size_y <= 0 || !(info->resolution > 0.0))
-    return c->fail(CSM_ERR_INVALID_ARG, "grid size and resolution must be positive");
+  if (const int st = check_grid_size(c, info)) return st;
   const int64_t ncell = (int64_t)info->size_x * info->size_y;
-  if (ncell >= ((int64_t)1 << 31)) return c->fail(CSM_ERR_INVALID_ARG, "grid larger than 2^31 cells");
   select_grid(c, cells);
   const bool same = c->owns_host_grid() && version >= 0 && (const void*)cells == c->key_cells &&
                     c->key_stride == -n_grids && version == c->key_version && info->size_x == c->key_sx &&
@@ -580,15 +614,7 @@ int csm_set_grid_stack(csm_ctx* c, const float* cells, int32_t n_grids, const cs
   if ((e = hipMemcpyAsync(c->grid_buf.p, cells, bytes, hipMemcpyHostToDevice, c->stream)) != hipSuccess)
     return c->hip_fail(e, "hipMemcpyAsync(grid stack)");
   if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return c->hip_fail(e, "hipStreamSynchronize(grid stack)");
-  c->d_grid = (const float*)c->grid_buf.p;
-  c->n_grids = n_grids;
-  c->has_grid = true;
-  c->int_checked = false;
-  c->key_cells = cells;
-  c->key_stride = -n_grids;  // never equal to a csm_set_grid stride
-  c->key_version = version;
-  c->key_sx = info->size_x;
-  c->key_sy = info->size_y;
+  adopt_grid(c, (const float*)c->grid_buf.p, n_grids, *info, cells, -n_grids, version);  // (no set_grid stride is < 0)
   return CSM_OK;
 }
 
@@ -614,8 +640,9 @@ int csm_set_grid_stack_gridmaps(csm_ctx* c, csm_gridmap* const* maps, int32_t n_
       return c->fail(CSM_ERR_INVALID_ARG, "stacked maps must share size, resolution and offset");
     min_index = std::min(min_index, b.map_update_index);
   }
+  const csm_map_info info = view_info(a, min_index);
+  if (const int st = check_grid_size(c, &info)) return st;
   const int64_t ncell = (int64_t)a.size_x * a.size_y;
-  if (ncell >= ((int64_t)1 << 31)) return c->fail(CSM_ERR_INVALID_ARG, "grid larger than 2^31 cells");
   hipError_t e;
   if ((e = c->grid_buf.ensure((size_t)ncell * (size_t)n_maps * sizeof(float))) != hipSuccess)
     return c->hip_fail(e, "hipMalloc(grid stack)");
@@ -626,18 +653,7 @@ int csm_set_grid_stack_gridmaps(csm_ctx* c, csm_gridmap* const* maps, int32_t n_
       return c->hip_fail(e, "hipMemcpyAsync(map stack)");
     csm::gridmap_add_read_fence(maps[i], c->stream);  // the map's next update after the copy (only)
   }
-  c->info.resolution = a.resolution;
-  c->info.offset_x = a.offset_x;
-  c->info.offset_y = a.offset_y;
-  c->info.size_x = a.size_x;
-  c->info.size_y = a.size_y;
-  c->info.update_index = min_index;
-  c->d_grid = (const float*)c->grid_buf.p;
-  c->n_grids = n_maps;
-  c->has_grid = true;
-  c->int_checked = false;
-  c->key_cells = nullptr;
-  c->key_version = -1;
+  adopt_grid(c, (const float*)c->grid_buf.p, n_maps, info);
   return CSM_OK;
 }
 

@@ -40,6 +40,7 @@
 #include "csm_pyramid.hpp"
 #include "csm_search_match.hpp"
 #include "csm_level_decision.hpp"
+#include "csm_grid_copies.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -439,7 +440,11 @@ struct GridState {
   int32_t outside_i = 0;
   double int_max_abs = 0.0;  // max |cell| (and |outside|) for the per-launch exactness bound
   uint64_t last_use = 0;     // csm_ctx::grid_clock when it was last selected
+  // cells of one fixed-point grid with its pad columns and zero rows (the stride of a stack's grids)
+  int64_t gridi_cells() const { return (int64_t)pitch * (info.size_y + csm::kGridiPadRows); }
 };
+
+using GridCopies = GridCopiesOf<DevBuf>;  // csm_grid_copies.hpp
 
 // A resident batch of scans: the context is one (the batch the next match
 // runs) and holds the queued and parked ones in csm_ctx::Staged::batch;
@@ -461,8 +466,8 @@ struct ScanBatch {
   }
 };
 
-static_assert(kMoveOnly<LaunchSlot> && kMoveOnly<GridState> && kMoveOnly<ScanBatch>,
-              "slots, grids and batches are exchanged, never copied");
+static_assert(kMoveOnly<LaunchSlot> && kMoveOnly<GridState> && kMoveOnly<ScanBatch> && kMoveOnly<GridCopies>,
+              "slots, grids, batches and the grid's copies are exchanged, never copied");
 
 }  // namespace csmh
 
@@ -513,35 +518,17 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState, csmh::Scan
   bool phase_kernel = true;   // v7 phase kernel for sub-cell window steps (CSM_KERNEL=v7 or unset)
   bool tiny_kernel = true;    // v8 tiny-window kernel, spans under one cell (CSM_KERNEL=v8 or unset)
   int phase_margin_log2 = 20; // CSM_PHASE_MARGIN_LOG2 (tests: a wider margin sends more beams to the exact path)
-  // the grid's palette: the byte copy of gridi (palette indices) and the
-  // palette, rebuilt when grid_gen moves on (the pair box kernel's source)
-  csmh::DevBuf pal_grid, pal_vals, pal_scratch;
-  csmh::DevBuf pal_strips;     // strip copies of pal_grid (v11 pair kernel; palettes of <= kPairMaxPal values)
-  bool pal_strips_ok = false;
   bool pair_kernel = true;     // v11 pair box kernel where the grid has a palette (CSM_KERNEL set: off)
-  csmh::DevBuf istrips;        // strip copies of gridi (the phase kernel's strip form)
-  uint64_t istrips_gen = 0;    // grid_gen they were built for
-  const int32_t* istrips_src = nullptr;
-  bool istrips_ok = false;
   bool phase_strips = true;    // CSM_PHASE_STRIPS=0: the phase kernel reads gridi row-major
-  int32_t pal_n = 0;           // palette size (0: none, e.g. more than kPalMax values)
-  uint64_t pal_gen = 0;        // grid_gen the palette was built for
-  const int32_t* pal_src = nullptr;  // ... and the gridi it was built from
-  // The pair kernel's map of uniform boxes (csm_palette.hip bg_geom), built
-  // with the strips and keyed like them. bg_ok: the pair kernel uses it (the
-  // share of set bits is at least kBgMinShare, or the knob forces it).
-  // CSM_BG_RUNS: 0 off, 1 (default) by the share, 2 always, 3 always with an
-  // empty map (the read's overhead alone, profiles/background_runs/speed.md).
-  csmh::DevBuf bg_map, bg_info;
-  bool bg_ok = false;
+  // CSM_BG_RUNS, the maps of uniform boxes: 0 off, 1 (default) by the share, 2
+  // always, 3 always with an empty map (the read's overhead alone,
+  // profiles/background_runs/speed.md)
   int bg_runs = 1;
-  double bg_share = 0.0;  // set bits / corners of the current grid(s)
-  // ... and the phase kernel's map of 5 x 5 boxes, built with it
-  csmh::DevBuf bg_map5;
-  bool bg5_ok = false;
-  double bg5_share = 0.0;
   bool box_kernel = true;     // v6 box kernel for one-cell window steps; any CSM_KERNEL other
                               // than v6 turns it off (CSM_KERNEL=v4: the LDS-DMA row kernel)
+  // The copies of the current fixed-point grid the kernels above read, keyed
+  // on (grid_gen, d_gridi) (csm_grid_copies.hpp; built by ensure_level_copies)
+  csmh::GridCopies copies;
   // Few-window launches (run_windows_small): the split kernel's slab and
   // arrival counters, the device copy of the windows and the finish's scratch
   // (ScanWork[nw] | AngleEntry[..] | need[nw] | list[nw + 1] | done counter),
@@ -856,10 +843,12 @@ void fill_scan_work_one(const Dims& D, const WindowPlan& W, int64_t pt_off, int3
 int ensure_int_grid(csm_ctx* c);
 void release_map_reader(csm_ctx* c);
 
-// csm_grid.cpp: the strip copies of gridi for the phase kernel (c->istrips_ok)
-int ensure_istrips(csm_ctx* c);
-// csm_grid.cpp: the palette copy of gridi for the v10 box kernel (c->pal_n = 0: none)
-int ensure_palette(csm_ctx* c);
+// csm_grid.cpp: the copies of gridi a level's decision needs (csm_ctx::copies):
+// the palette family where the pair kernel may run, the strips of gridi (and
+// the palette, for the map of 5 x 5 boxes) for a phase level
+int ensure_level_copies(csm_ctx* c, bool pair, bool phase);
+// ... and those copies as the chosen kernel's LevelWork fields
+void level_work_copies(const csm_ctx* c, ScoreKernel kernel, LevelWork& L);
 
 // csm_launch.cpp
 int wait_flag(csm_ctx* c, const PendingRun& p, const int32_t* flag = nullptr);

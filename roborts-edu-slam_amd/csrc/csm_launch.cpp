@@ -282,7 +282,7 @@ LevelWork make_level_work(const csm_ctx* c, const csm_param& P, const Dims& D, c
   L.int_scale = std::ldexp(1.0, -c->int_exp);
   L.outside_i = c->outside_i;
   L.pitch = c->pitch;
-  L.gridi_stride = (int64_t)c->pitch * (c->info.size_y + csm::kGridiPadRows);
+  L.gridi_stride = c->gridi_cells();
   return L;
 }
 
@@ -570,7 +570,7 @@ int Launch::validate() {
 int Launch::decide() {
   const bool use_int = c->int_ok && S.in_range;
   const bool pad_ok = c->pitch >= c->info.size_x + csm::kGridiPadCols;
-  const int64_t gridi_cells = (int64_t)c->pitch * (c->info.size_y + csm::kGridiPadRows);
+  const int64_t gridi_cells = c->gridi_cells();
   sig = signalled_finish(c, mode);
   LevelCaps K;
   K.int_grid = c->int_ok;
@@ -591,18 +591,13 @@ int Launch::decide() {
   }
   // v11: the box read through the grid's palette (one byte per cell), pairs
   // of equal-count runs over the strip copies (palettes of <= 16 values);
-  // otherwise the v6 kernel reads gridi
-  int st;
-  if (dec.box && c->pair_kernel && csm::box_pair_supported(D.n_space)) {
-    if ((st = ensure_palette(c)) != CSM_OK) return st;
-    F.pair_ok = c->pal_n > 0 && gridi_cells <= INT32_MAX && c->pal_strips_ok;
-  }
+  // otherwise the v6 kernel reads gridi. The phase kernel's strip form reads
+  // its own copies
+  const bool pair = dec.box && c->pair_kernel && csm::box_pair_supported(D.n_space);
+  if (const int st = ensure_level_copies(c, pair, dec.phase)) return st;
+  F.pair_ok = pair && c->copies.pair_ok() && gridi_cells <= INT32_MAX;
   const int64_t tile_n = (D.n_space + 15) / 16;
   F.tiled_ok = c->box_kernel && f == 1.0 && pad_ok && (int64_t)nw * tile_n * tile_n * D.n_angles <= INT32_MAX;
-  if (dec.phase && c->phase_strips && (st = ensure_istrips(c)) != CSM_OK) return st;
-  // the phase kernel's map of uniform boxes is made from the palette's index grid
-  if (dec.phase && c->phase_strips && c->pair_kernel && c->bg_runs != 0 && (st = ensure_palette(c)) != CSM_OK)
-    return st;
   shape = launch_shape(dec, D.n_angles, D.n_space, F);
   if (shape.bps * nr() > INT32_MAX) return c->fail(CSM_ERR_UNSUPPORTED, "window too large for one launch");
   stride = score_stride(c, D, mode);
@@ -626,39 +621,7 @@ int Launch::level_work(const std::vector<int64_t>& pt_offsets, const std::vector
   // level's spans on one kernel instantiation
   L.max_n_used = dec.max_n_used;
   L.tile_n = tiled ? shape.ktiles : 0;
-  if (shape.kernel == ScoreKernel::kBoxPair) {
-    const csm::StripGeom SG = csm::strip_geom(c->info.size_x, c->info.size_y);
-    L.pal_n = c->pal_n;
-    L.pal_grid = (const uint8_t*)c->pal_grid.p;
-    L.pal_vals = (const int32_t*)c->pal_vals.p;
-    L.pal_stride = (int64_t)c->pitch * (c->info.size_y + csm::kGridiPadRows);
-    L.pal_strips = (const uint8_t*)c->pal_strips.p;
-    L.strip_bytes = (int32_t)SG.strip_bytes;
-    L.strip_copy_bytes = (int32_t)SG.copy_bytes;
-    L.strip_grid_bytes = SG.grid_bytes;
-    if (c->bg_ok) {
-      const csm::BgGeom BG = csm::bg_geom(c->info.size_x, c->info.size_y);
-      L.bg_map = (const uint8_t*)c->bg_map.p;
-      L.bg_info = (const int32_t*)c->bg_info.p;
-      L.bg_tiles8 = BG.tiles_x * 8;
-      L.bg_grid_bytes = (int32_t)BG.grid_bytes;
-    }
-  }
-  if (shape.kernel == ScoreKernel::kPhase && c->phase_strips && c->istrips_ok) {
-    const csm::StripGeom SG = csm::istrip_geom(c->info.size_x, c->info.size_y);
-    L.istrips = (const int32_t*)c->istrips.p;
-    L.istrip_bytes = (int32_t)SG.strip_bytes;
-    L.istrip_copy_bytes = (int32_t)SG.copy_bytes;
-    L.istrip_grid_bytes = SG.grid_bytes;
-    if (c->pair_kernel && c->bg_runs != 0 && c->bg5_ok && c->pal_gen == c->grid_gen && c->pal_src == c->d_gridi) {
-      const csm::BgGeom BG = csm::bg_geom(c->info.size_x, c->info.size_y);
-      L.bg_map5 = (const uint8_t*)c->bg_map5.p;
-      L.bg_info = (const int32_t*)c->bg_info.p;
-      L.bg_tiles8 = BG.tiles_x * 8;
-      L.bg_grid_bytes = (int32_t)BG.grid_bytes;
-      L.pal_vals = (const int32_t*)c->pal_vals.p;
-    }
-  }
+  level_work_copies(c, shape.kernel, L);
   L.n_cols = (int32_t)shape.n_cols;
   L.ktiles = shape.ktiles;
   L.col_blocks = (int32_t)shape.col_blocks;

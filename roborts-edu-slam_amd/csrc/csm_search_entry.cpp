@@ -152,8 +152,7 @@ int search_stage(csm_ctx* c, const csm_param* param, const Geometry& G, const Se
   L.outside_i = c->outside_i;
   L.int_mode = 1;
   L.int_scale = std::ldexp(1.0, -c->int_exp);
-  in.level0 = csm::PyrGrid{c->d_gridi,
-                           (int64_t)c->pitch * (c->info.size_y + csm::kGridiPadRows), c->pitch, 0,
+  in.level0 = csm::PyrGrid{c->d_gridi, c->gridi_cells(), c->pitch, 0,
                            c->info.size_x, c->info.size_y, 0, c->info.size_x, 0, 0};
   in.n_grids = c->n_grids;
   in.grid_gen = c->grid_gen;
