@@ -113,7 +113,9 @@ typedef struct csm_best {
 
 /* Per-kernel accounting collected with HIP events on the context's stream
  * while profiling is on (csm_set_profiling). algorithmic_bytes counts one
- * fp32 grid read per summed beam per candidate (4*B bytes per scoring). */
+ * fp32 grid read per summed beam per candidate (4*B bytes per scoring).
+ * launches of a scoring kernel counts its launches: a level sent out in
+ * spans is as many (and is listed again under "span2:<name>"). */
 typedef struct csm_kernel_stat {
   char name[48];
   int64_t launches;
@@ -251,7 +253,12 @@ int csm_load_scans_async(csm_ctx* ctx, int32_t n_scans, const double* points_xy,
  * are final once the next submit, csm_scan_matchers_wait, or any other call on
  * the context returns (every other entry point completes a pending batch
  * first); they must stay valid until then. Results equal
- * csm_scan_matchers_loaded's bit for bit. */
+ * csm_scan_matchers_loaded's bit for bit. A submitted batch whose coarse
+ * level sums more than 512 beams goes through the levels in one part (one
+ * scoring launch and one fast finish pass per level over all its windows, the
+ * coarse level in spans; the other batch's launches cover the host), others
+ * in two as the synchronous calls do; CSM_SUBMIT_PARTS=1 or 2 forces either
+ * (A/B runs, tests), an explicit CSM_PIPELINE_PARTS keeps its parts. */
 int csm_scan_matchers_submit(csm_ctx* ctx, const csm_param levels[3], int32_t use_fine, double* poses, double* covs,
                              double* scores);
 int csm_scan_matchers_wait(csm_ctx* ctx);

@@ -3,6 +3,7 @@
 // ScanMatchers driver over the resident batch (csm_scan_matchers*, synchronous
 // or submitted; csm_pipeline.cpp, csm_batch.cpp).
 #include "csm_driver_internal.hpp"
+#include "csm_submit_order.hpp"
 
 using namespace csmh;
 
@@ -131,8 +132,10 @@ int csm_scan_matchers_submit(csm_ctx* c, const csm_param levels[3], int32_t use_
   bool fast = false;
   for (int l = 0; l < n_levels; ++l) fast |= levels[l].type == CSM_FAST;
   const int32_t* grid = c->scan_grid.empty() ? nullptr : c->scan_grid.data();
-  const int K = std::max(2, std::min(c->pipeline_parts, csm_ctx::kMaxParts));
-  if (n_scans == 0 || fast || grid || n_scans < c->pipeline_min || 2 * K > csm_ctx::kMaxParts) {
+  // one part where the other batch's launches cover the host (submit_parts), else the driver's parts
+  const int K = submit_parts(c->submit_parts, c->pipeline_parts_set, std::min(c->pipeline_parts, csm_ctx::kMaxParts),
+                             coarse_device_bound(c, levels, n_levels));
+  if (n_scans == 0 || fast || grid || n_scans < c->pipeline_min || K > PipeState::kParts) {
     // nothing to overlap (or no second set of buffer slots): the batch completes here
     if ((st = prior_last_launches()) != CSM_OK || (st = pipe_drain(c)) != CSM_OK) return st;
     return matchers_loaded_locked(c, levels, use_fine, poses, covs, scores);
@@ -145,21 +148,27 @@ int csm_scan_matchers_submit(csm_ctx* c, const csm_param levels[3], int32_t use_
   if (J.pending && ((st = prior_last_launches()) != CSM_OK || (st = pipe_drain(c)) != CSM_OK))
     return st;  // (cannot happen: submits alternate)
   PipeMode mode(c);
-  job_setup(c, J, n_scans, c->scan_off.data(), levels, n_levels, poses, covs, nullptr, nullptr, K, PS.next * K,
-            true);
+  job_setup(c, J, n_scans, c->scan_off.data(), levels, n_levels, poses, covs, nullptr, nullptr, K,
+            PS.next * PipeState::kParts, true);
   J.own_sum.assign((size_t)n_scans, 0.0);
   J.sum = J.own_sum.data();
   J.scores = scores;
   // this batch's first part's first level, the previous batch's last launch
-  // (its last part's last hand-off), this batch's other parts' first level,
-  // then the previous batch's completion while those score, then the rest of
-  // this batch up to its last part's last hand-off
-  if ((st = job_begin(c, J, 0)) != CSM_OK) return pipe_abort(c, st);
-  if ((st = prior_last_launches()) != CSM_OK) return pipe_abort(c, st);
-  for (int h = 1; h < K; ++h)
-    if ((st = job_begin(c, J, h)) != CSM_OK) return pipe_abort(c, st);
-  if (P.pending && (st = job_finish(c, P)) != CSM_OK) return pipe_abort(c, st);
-  if ((st = job_levels(c, J)) != CSM_OK) return pipe_abort(c, st);
+  // (its last part's last hand-off), then this batch's other levels around the
+  // previous batch's completion, up to its own last part's last hand-off: the
+  // order is csm_submit_order.hpp's, by the two batches' parts
+  const SubmitOrder order = submit_order(K, P.pending ? P.K : 0, n_levels, c->defer_last_handoff);
+  for (int i = 0; i < order.n; ++i) {
+    const SubmitOp& op = order.op[i];
+    switch (op.step) {
+      case SubmitStep::kBegin: st = job_begin(c, J, op.part); break;
+      case SubmitStep::kHandoff: st = job_handoff(c, J, op.level, op.part); break;
+      case SubmitStep::kPriorLast: st = prior_last_launches(); break;
+      case SubmitStep::kPriorFinish: st = job_finish(c, P); break;
+    }
+    if (st != CSM_OK) return pipe_abort(c, st);
+  }
+  job_launched(c, J);
   PS.next ^= 1;
   if (c->profiling) {
     c->t_exit = now_ms();

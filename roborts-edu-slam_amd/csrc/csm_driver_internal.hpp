@@ -96,7 +96,7 @@ struct LevelRun {
 // (into the other half of the buffer slots), then the deferred completion runs
 // while that one scores -- the device no longer idles between batches.
 struct PipeJob {
-  int K = 2, n_levels = 0, slot0 = 0;  // parts, levels, the parts' first buffer slot
+  int K = 2, n_levels = 0, slot0 = 0;  // parts (1: submitted batches only), levels, the parts' first buffer slot
   int first_windows = 0;                // the first part's first span (level_begin_split)
   int32_t n_scans = 0;
   // A submitted batch's are its ScanBatch::scan_off's data: the batch parks in
@@ -124,7 +124,10 @@ struct PipeJob {
 
 struct PipeState {
   PipeJob job[2];
-  int next = 0;  // the job slot the next submit takes (its parts: slots next * K ...)
+  int next = 0;  // the job slot the next submit takes (its parts: buffer slots next * kParts ...)
+  // buffer slots of a job slot: one- and two-part batches alternate in one
+  // context, so a job's slots do not depend on its own parts
+  static constexpr int kParts = csm_ctx::kMaxParts / 2;
 };
 
 // The driver's knobs for a pipelined batch: every part on the throughput
@@ -141,6 +144,13 @@ struct PipeMode {
     c->early_now = false;
   }
 };
+
+// The coarse level sums enough beams for the device to bound the step: a
+// submitted batch then sends its first span out early and may take one part
+// (csm_submit_order.hpp); below that the step is host-bound (csm_host.hpp).
+inline bool coarse_device_bound(const csm_ctx* c, const csm_param* levels, int n_levels) {
+  return n_levels > 0 && levels[0].use_point_size > c->first_windows_submit_min_use;
+}
 
 // csm_level.cpp
 int live_lists(const csm_param* levels, int n_levels, int l);
@@ -159,7 +169,9 @@ void job_setup(csm_ctx* c, PipeJob& J, int32_t n_scans, const int64_t* offsets, 
                int n_levels, double* poses, double* covs, double* sum, const int32_t* scan_grid, int K, int slot0,
                bool submitted = false);
 int job_begin(csm_ctx* c, PipeJob& J, int h);
+int job_handoff(csm_ctx* c, PipeJob& J, int l, int h);
 int job_levels(csm_ctx* c, PipeJob& J);
+void job_launched(const csm_ctx* c, PipeJob& J);
 int job_finish(csm_ctx* c, PipeJob& J);
 int pipe_abort(csm_ctx* c, int st);
 int pipe_last_launches(csm_ctx* c);

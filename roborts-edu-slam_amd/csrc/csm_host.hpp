@@ -342,6 +342,7 @@ struct PendingRun {
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, done = nullptr;
   hipEvent_t ev_fast = nullptr;  // after the fast finish pass, when the exact pass runs on x_stream
   hipEvent_t gap0 = nullptr, gap1 = nullptr;  // a two-span level: not kernel time between these
+  int dispatches = 1;  // scoring launches the level went out in (its spans): the stats' `launches` of kname
   const int32_t* flags = nullptr;  // need-exact flags on the host (profiling)
   int n_flags = 0;
   // few-window launches: the finish writes FinishOut here (host memory) and
@@ -399,6 +400,7 @@ struct LaunchSlot {
   Event ev_k;     // a launch's kernels are done
   Event ev_fast;  // the fast finish pass ended: the exact pass on x_stream waits for it
   bool span_gap = false;
+  int span_count = 0;  // scoring launches of the slot's level so far (PendingRun::dispatches)
   int32_t list_tag = 0;  // host signal: the tag of the slot's latest scoring call (run_windows)
   // the fused finish: a level's first span is out but its last window's span
   // is not (a level that failed on the host between them leaves level_ctr and
@@ -669,6 +671,14 @@ struct csm_ctx : csmh::CtxStreams, csmh::LaunchSlot, csmh::GridState, csmh::Scan
   // candidates, 0.354 against 0.558 ms at 8,649)
   int64_t list_reduce_min = 8192;
   int pipeline_parts = 2;    // parts in flight (CSM_PIPELINE_PARTS: 2..kMaxParts; 2 measured fastest)
+  bool pipeline_parts_set = false;  // CSM_PIPELINE_PARTS was given: submitted batches take it too
+  // Submitted batches (csm_submit_order.hpp, submit_parts): one part for a
+  // device-bound coarse level, else pipeline_parts; 1 or 2 forces it
+  // (CSM_SUBMIT_PARTS; 0: by the rule). Headline, five interleaved pairs: two
+  // parts 1.950 ms a step, one part 1.848 (profiles/submit_single_part/speed.md).
+  // The synchronous calls always take pipeline_parts: no other batch covers the host.
+  int submit_parts = 0;
+  bool single_split_handoff = false;  // a single part's last hand-off in two spans (CSM_SINGLE_SPLIT_HANDOFF)
   int first_windows = 128;   // level_begin_split: windows the first part's first launch takes (CSM_FIRST_WINDOWS; 0: one launch)
   // submitted batches (the device has the previous batch's work queued): a
   // 512-window first span, so the batch boundary's host planning covers 512

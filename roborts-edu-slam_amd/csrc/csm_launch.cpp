@@ -105,11 +105,15 @@ int account_run(csm_ctx* c, const PendingRun& p) {
       if ((e = hipEventElapsedTime(&g, p.gap0, p.gap1)) != hipSuccess) return c->hip_fail(e, "hipEventElapsedTime");
       ms -= g;
     }
+    // `launches` counts scoring launches: a level sent out in spans is as many
+    // (a single-part batch's coarse level is one level and two or three launches)
     c->account(p.kname, ms, p.alg_bytes, p.scorings);
-    if (p.gap0) {  // the same launch again under "span2:": two dispatches, each with its own ramp and tail
+    if (p.dispatches > 1) c->account_count(p.kname, p.dispatches - 1);
+    if (p.gap0) {  // the same launches again under "span2:": several dispatches, each with its own ramp and tail
       char nm[48];  // (its bytes too: the one-dispatch launches' bytes per ms are then known)
       std::snprintf(nm, sizeof(nm), "span2:%.41s", p.kname);
       c->account(nm, ms, p.alg_bytes, 0.0);
+      if (p.dispatches > 1) c->account_count(nm, p.dispatches - 1);
     }
     if (p.device_finish) {
       if ((e = hipEventElapsedTime(&ms, p.ev1, p.ev2)) != hipSuccess) return c->hip_fail(e, "hipEventElapsedTime");
@@ -819,6 +823,7 @@ int Launch::scoring() {
   } else if ((e = c->scores.ensure((size_t)nw * (size_t)stride * sizeof(double))) != hipSuccess) {
     return c->hip_fail(e, "hipMalloc(scores)");
   }
+  if (sp.score) c->span_count = w0 == 0 ? 1 : c->span_count + 1;
   if (sp.score &&  // (otherwise scored by earlier calls)
       (e = launch_score(shape, L, PT, (const ScanWork*)c->scans.p + w0, (const double*)c->pts.p,
                         (const AngleEntry*)c->angles.p, best ? nullptr : (double*)c->scores.p,
@@ -932,6 +937,8 @@ void Launch::fill_pending(const char* kname, PendingRun& p) {
     p.gap1 = c->ev_g1;
     c->span_gap = false;
   }
+  p.dispatches = std::max(1, c->span_count);
+  c->span_count = 0;
   p.fin_host = sig_out;
   p.host_flag = SA.host_flag;
   p.fast_flag = SA.host_fast_flag;

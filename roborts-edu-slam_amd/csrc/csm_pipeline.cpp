@@ -3,6 +3,7 @@
 // csm_driver_internal.hpp), and submitted batches: one batch's last level
 // pending while the next one's first launch scores.
 #include "csm_driver_internal.hpp"
+#include "csm_submit_order.hpp"
 
 namespace csmh {
 namespace {
@@ -86,6 +87,13 @@ int job_skip(const csm_ctx* c, const PipeJob& J, int l) {
   return c->skip_dead_lists ? live_lists(J.levels, J.n_levels, l) : 0;
 }
 
+}  // namespace
+
+PipeState& pipe_of(csm_ctx* c) {
+  if (!c->pipe) c->pipe = new PipeState();
+  return *static_cast<PipeState*>(c->pipe);
+}
+
 // The level transition (l -> l + 1) of part h.
 int job_handoff(csm_ctx* c, PipeJob& J, int l, int h) {
   const int32_t s0 = J.first[h];
@@ -95,28 +103,25 @@ int job_handoff(csm_ctx* c, PipeJob& J, int l, int h) {
   // step, profiles/r05/experiments/ab_profile_first_level.txt)
   const bool timed = c->profiling;
   c->profiling = timed && !c->profile_first_level;
+  // the last part's last hand-off in two spans: with two parts only the other
+  // part's short last level runs meanwhile; a single part's runs under the
+  // next batch's whole coarse level (CSM_SINGLE_SPLIT_HANDOFF=1: split too)
+  const bool split = (J.K > 1 ? c->split_last_handoff : c->single_split_handoff) && h == J.K - 1 && l + 2 == J.n_levels;
   const int st = with_slot(c, J, h, [&] {
     return level_end_begin(c, J.R[l & 1][h], J.R[(l + 1) & 1][h], J.count[h], J.offsets + s0, J.levels[l + 1],
                            J.poses + 3 * (size_t)s0, J.covs + 9 * (size_t)s0, J.resp.data() + s0, J.sum + s0,
                            J.scan_grid ? J.scan_grid + s0 : nullptr, job_skip(c, J, l + 1),
-                           c->split_last_handoff && h == J.K - 1 && l + 2 == J.n_levels);
+                           split);
   });
   c->profiling = timed;
   return st;
 }
 
 // The last part's last level transition (the last launch of J).
-int job_last_handoff(csm_ctx* c, PipeJob& J) {
+static int job_last_handoff(csm_ctx* c, PipeJob& J) {
   if (!J.pending || J.last_handoff_done) return CSM_OK;
   J.last_handoff_done = true;
   return job_handoff(c, J, J.n_levels - 2, J.K - 1);
-}
-
-}  // namespace
-
-PipeState& pipe_of(csm_ctx* c) {
-  if (!c->pipe) c->pipe = new PipeState();
-  return *static_cast<PipeState*>(c->pipe);
 }
 
 void job_setup(csm_ctx* c, PipeJob& J, int32_t n_scans, const int64_t* offsets, const csm_param* levels,
@@ -126,9 +131,7 @@ void job_setup(csm_ctx* c, PipeJob& J, int32_t n_scans, const int64_t* offsets, 
   // submitted batches split their first span only when the coarse level sums
   // many beams: below that the step is host-bound and the extra launch costs
   // more than the shorter planning at the batch boundary (csm_host.hpp)
-  J.first_windows = !submitted ? c->first_windows
-                    : (n_levels > 0 && levels[0].use_point_size > c->first_windows_submit_min_use) ? c->first_windows_submit
-                                                                                                   : 0;
+  J.first_windows = !submitted ? c->first_windows : coarse_device_bound(c, levels, n_levels) ? c->first_windows_submit : 0;
   const int permille = submitted ? c->part0_permille_submit : c->part0_permille;
   J.n_levels = n_levels;
   J.slot0 = slot0;
@@ -146,11 +149,14 @@ void job_setup(csm_ctx* c, PipeJob& J, int32_t n_scans, const int64_t* offsets, 
   // larger first part shortens what nothing hides, the last part's
   // super-fine completion at the end of the call and its fine -> super-fine
   // hand-off (the device has only part 0's super-fine level to run meanwhile)
+  // (a single part, submitted batches only, is the whole batch)
   const int64_t n0 = (K == 2 && permille > 0) ? (int64_t)n_scans * permille / 1000
                                                         : (int64_t)n_scans / K;
-  for (int h = 0; h < K; ++h) {
-    J.first[h] = h == 0 ? 0 : (int32_t)(n0 + (int64_t)(n_scans - n0) * (h - 1) / (K - 1));
-    J.count[h] = (h == 0 ? (int32_t)n0 : (int32_t)(n0 + (int64_t)(n_scans - n0) * h / (K - 1))) - J.first[h];
+  J.first[0] = 0;
+  J.count[0] = (int32_t)n0;
+  for (int h = 1; h < K; ++h) {  // (K >= 2 here)
+    J.first[h] = (int32_t)(n0 + (int64_t)(n_scans - n0) * (h - 1) / (K - 1));
+    J.count[h] = (int32_t)(n0 + (int64_t)(n_scans - n0) * h / (K - 1)) - J.first[h];
   }
   J.resp.assign((size_t)n_scans, 0.0);
   for (auto& row : J.R)
@@ -186,12 +192,17 @@ int job_levels(csm_ctx* c, PipeJob& J) {
   int st;
   for (int l = 0; l + 1 < n_levels; ++l)
     for (int h = 0; h < K; ++h) {
-      if (c->defer_last_handoff && l + 2 == n_levels && h == K - 1) continue;
+      if (handoff_deferred(l, h, K, n_levels, c->defer_last_handoff)) continue;
       if ((st = job_handoff(c, J, l, h)) != CSM_OK) return st;
     }
-  J.pending = true;
-  J.last_handoff_done = n_levels < 2 || !c->defer_last_handoff;
+  job_launched(c, J);
   return CSM_OK;
+}
+
+// J's launches are out up to the deferred hand-off: its completion is owed.
+void job_launched(const csm_ctx* c, PipeJob& J) {
+  J.pending = true;
+  J.last_handoff_done = J.n_levels < 2 || !c->defer_last_handoff;
 }
 
 // J's last level: every part's windows completed, responses summed (and the

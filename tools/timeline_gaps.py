@@ -30,8 +30,13 @@ def main():
     main_q = max(by_q, key=lambda q: sum("score_phase" in r["Kernel_Name"] for r in by_q[q]))
     seq = by_q[main_q]
     # a step starts at a coarse (box) launch that follows a tiny-window launch's finish
+    # (parts = 1, a single-part batch: the other batch's super-fine level and this batch's
+    # fine level lie between the coarse level's spans and the next step's: its first span)
+    parts = int(sys.argv[3]) if len(sys.argv) > 3 else 2
+    back = 3 if parts > 1 else 5
     starts = [i for i, r in enumerate(seq) if "score_box" in r["Kernel_Name"] and i > 0 and
-              any("score_tiny" in seq[j]["Kernel_Name"] for j in range(max(0, i - 3), i))]
+              (parts > 1 or "score_box" not in seq[i - 1]["Kernel_Name"]) and
+              any("score_tiny" in seq[j]["Kernel_Name"] for j in range(max(0, i - back), i))]
     starts = starts[-(steps + 1):]
     if len(starts) < 2:
         sys.exit("fewer than two steps found")
@@ -41,7 +46,6 @@ def main():
     t_total = 0.0
     # steps: tiny-window launches / parts (a step's coarse launches can come
     # in two spans and the parts interleave across batches)
-    parts = int(sys.argv[3]) if len(sys.argv) > 3 else 2
     a, b = starts[0], starts[-1]
     n = max(1, sum("score_tiny" in seq[i]["Kernel_Name"] for i in range(a, b)) // parts)
     t_total = (int(seq[b]["Start_Timestamp"]) - int(seq[a]["Start_Timestamp"])) / 1e3
