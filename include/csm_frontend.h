@@ -24,7 +24,13 @@
  * the oracle's restatement of the same loop).
  *
  * Threading: one caller at a time per front-end (the reference serialises the
- * front-end in its ROS callback).
+ * front-end in its ROS callback). The one exception is
+ * csm_frontend_publish_map, which one other thread may call while this one is
+ * in any other entry point (the reference's PublishMapThread): the front end
+ * holds SlamProcessor's map_mutex_ over the regions the reference holds it
+ * (slam_processor.cpp:137 the match, :346 CorrectPoseAndMap's rebuild, :466
+ * CreateAllMap, :533 UpdateMap, :576 the map check). csm_frontend_destroy is
+ * not part of the exception: the publisher thread has ended before it.
  */
 #ifndef ROBORTS_CSM_FRONTEND_H
 #define ROBORTS_CSM_FRONTEND_H
@@ -117,6 +123,23 @@ int csm_frontend_matcher(csm_frontend* fe, csm_ctx** ctx);
 int csm_frontend_correct_pose_and_map(csm_frontend* fe, int32_t n, const int32_t* ids, const double* poses);
 /* Kept scans so far (*n in: capacity of poses, out: count) and their poses. */
 int csm_frontend_kept_scans(csm_frontend* fe, int32_t* n, double* poses);
+/* SlamNode::PublishMapThread's loop body (roborts_slam_node.cpp:361-471)
+ * without the ROS message: under the map mutex, the PubMap's
+ * map_update_index (-1 while the PubMap is null, before the first scan) goes
+ * to info->map_update_index; when the map is null or the index equals
+ * last_index (:382-383) the call returns CSM_OK with *data = NULL and the
+ * rest of info zero. Otherwise csm_gridmap_occupancy_grid_begin (bound-box
+ * form) runs under the mutex, the mutex is released and
+ * csm_gridmap_occupancy_grid_end waits: the front end is held up for the
+ * enqueue, not for the kernel and the copy (the reference's publisher holds
+ * the mutex through its whole loop over the cells). *data: info->height *
+ * info->width states, row-major, in the PubMap's buffer, valid until the next
+ * call or the front end's destruction. Callable from one thread other than
+ * the one in the front end's other entry points; errors are returned as
+ * status only (csm_gridmap_last_error of the PubMap has the text) so that
+ * csm_frontend_last_error stays the processing thread's. */
+int csm_frontend_publish_map(csm_frontend* fe, int32_t last_index, csm_occupancy_grid_info* info,
+                             const int8_t** data);
 /* Host wall time (ms) of the last csm_frontend_process call's phases:
  * [0] points scaled to the three resolutions, [1] the 3-level match
  * (ScanMatchers::ScanMatch), [2] the map check (MapCheckPenalize), [3] the

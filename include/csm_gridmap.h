@@ -30,6 +30,9 @@
  *                             (with use_reset_speedup: ResetValueSpeedup grid_map_base.h:112-117)
  *   csm_gridmap_feedback_penalty OccuGridMap::MapFeedbackResponsePenalty occu_grid_map.h:331-392
  *   csm_gridmap_info / csm_gridmap_download   GridMapBase getters and GetCell reads
+ *   csm_gridmap_states / csm_gridmap_occupancy_grid*   GetGridStates over a box, and the
+ *                             box, size and origin of SlamNode::PublishMapThread
+ *                             (roborts_slam_node.cpp:355-488; see "the map publisher" below)
  *   csm_set_grid_gridmap      the scan matcher reads this map's probabilities
  *                             (ScanMatchers::ScanMatch on fine_map, scan_matchers.h:238-256)
  *
@@ -123,6 +126,59 @@ int csm_gridmap_download(csm_gridmap* map, float* prob, float* pass_count, float
 /* Device pointer of the probability array (row-major y*size_x + x). Valid
  * until the next call that grows or destroys the map. */
 int csm_gridmap_device_prob(csm_gridmap* map, const float** device_prob);
+
+/* ---- the map publisher ---------------------------------------------------
+ * What SlamNode::PublishMapThread (roborts_slam_node.cpp:355-488) computes of
+ * a nav_msgs::OccupancyGrid, without the ROS message: the cells' states
+ * (100 occupied, 0 free, -1 unknown), classified on the device, and the
+ * grid's origin, resolution, width and height. */
+typedef struct csm_occupancy_grid_info {
+  double origin_x, origin_y, resolution;   /* map_.info.origin.position, .resolution */
+  int32_t width, height;                   /* map_.info.width / .height               */
+  int32_t start_x, start_y;                /* first cell of the box                   */
+  int32_t map_update_index;                /* the map state the grid shows            */
+  int32_t reserved;
+} csm_occupancy_grid_info;
+
+/* GetGridStates(x, y) (map/occu_grid_map.h -> CountCellFunctions::GetGridStates
+ * map/grid_map_cell.h:125-136, ProbabilityCellFunctions:: :367-375) of the
+ * cells (x0 + i, y0 + j), i < w, j < h, as the node's loop writes them
+ * (roborts_slam_node.cpp:444-469): out[j * w + i], copied to the host before
+ * the call returns. The cell is GetCell(x, y), linear index y * size_x + x
+ * (grid_map_base.h:315-317), so x = size_x reads the next row's first cell;
+ * a negative x or y, or an index past the array, gives -1. Negative w or h
+ * and w * h >= 2^31 are CSM_ERR_INVALID_ARG; w * h == 0 does nothing. */
+int csm_gridmap_states(csm_gridmap* map, int32_t x0, int32_t y0, int32_t w, int32_t h, int8_t* out);
+/* The published grid's geometry alone (a caller sizes its buffer from it).
+ * full_map = 0: the bound box, GetStartGrid .. GetEndGrid with both ends
+ * (grid_map_base.h:319-328), GetBoundSizeX/Y (util/boundbox.h:99-111), origin
+ * GetWorldCoords(GetStartGrid()) - GetCellLength() / 2
+ * (roborts_slam_node.cpp:427-436); a bound box never set gives 0 x 0 at
+ * start (0, 0). full_map != 0: kDisplayFullMap (:391-404), every cell, origin
+ * from GetWorldCoords(0, 0). */
+int csm_gridmap_occupancy_grid_info(csm_gridmap* map, int32_t full_map, csm_occupancy_grid_info* info);
+/* Start one grid: under the map's lock, the info as above, the states kernel
+ * on the map's stream and one device-to-host copy into a pinned buffer the map
+ * owns; returns without waiting for either. The map's later updates run on
+ * the same stream, so the grid is the state info->map_update_index names
+ * whatever is enqueued after it. A second _begin before _end waits for the
+ * first. */
+int csm_gridmap_occupancy_grid_begin(csm_gridmap* map, int32_t full_map, csm_occupancy_grid_info* info);
+/* Wait for the grid _begin started (outside the map's lock: updates of the
+ * map go on meanwhile) and hand out the map's buffer, height * width bytes,
+ * valid until the next _begin on this map or its destruction. Without a
+ * _begin: CSM_ERR_INVALID_ARG. */
+int csm_gridmap_occupancy_grid_end(csm_gridmap* map, const int8_t** data);
+/* _begin, _end and a copy into data (the whole of roborts_slam_node.cpp:
+ * 386-471 for one map). capacity < width * height: CSM_ERR_INVALID_ARG, info
+ * filled, data untouched. */
+int csm_gridmap_occupancy_grid(csm_gridmap* map, int32_t full_map, csm_occupancy_grid_info* info, int8_t* data,
+                               int64_t capacity);
+
+/* Diagnostics (no reference counterpart): the states kernel of that grid alone,
+ * `repeats` launches back to back on the map's stream between two HIP events;
+ * *ms = their mean time. An empty grid is CSM_ERR_INVALID_ARG. */
+int csm_gridmap_occupancy_grid_kernel_ms(csm_gridmap* map, int32_t full_map, int32_t repeats, double* ms);
 
 /* Point the scan matcher at this map (borrowed, like csm_set_grid_device):
  * size, resolution, offset and update index come from the map.

@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -66,6 +67,9 @@ struct csm_frontend {
   csm_ctx* ctx = nullptr;         // matcher on the fine map
   csm_ctx* ctx_coarse = nullptr;  // Gauss-Newton matcher on the coarse map (use_optimize_scan_match)
   csm_gridmap* maps[3] = {nullptr, nullptr, nullptr};
+  // SlamProcessor::map_mutex_ (slam_processor.h; locked at slam_processor.cpp:137,
+  // 346, 466, 533, 576): the maps against csm_frontend_publish_map's thread
+  std::mutex map_mu;
   int32_t data_index = 0;  // scans kept so far (SensorDataManager::current_data_index_ + 1)
   double current_pose[3] = {0, 0, 0};
   double last_odom[3] = {0, 0, 0};
@@ -192,6 +196,7 @@ int csm_frontend_process(csm_frontend* f, const double* pts, int32_t n, const do
   };
   const bool first = f->data_index == 0;  // IsFirstRangeData
   if (first) {
+    std::lock_guard<std::mutex> map_lock(f->map_mu);  // :466
     if ((st = create_all_maps(f)) != CSM_OK) return st;
     f->current_pose[0] = f->current_pose[1] = f->current_pose[2] = 0.0;
   }
@@ -210,15 +215,18 @@ int csm_frontend_process(csm_frontend* f, const double* pts, int32_t n, const do
     csm::MatchersConfig cfg{p.levels, p.use_optimize_scan_match, p.optimize_failed_cost, p.optimize, p.range_max};
     double score = 0.0;
     std::string why;
+    std::unique_lock<std::mutex> map_lock(f->map_mu);  // :137, held over the match
     if ((st = csm::scan_matchers_on_maps(f->ctx, f->ctx_coarse, f->maps[CSM_COARSE_MAP], f->maps[CSM_FINE_MAP],
                                          f->coarse_pts.data(), f->fine_pts.data(), n, cfg, 1, pose, cov, &score,
                                          &r->optimize_cost, &why)) != CSM_OK)
       return f->fail(st, why);
+    map_lock.unlock();
     std::memcpy(r->match_pose, pose, sizeof(pose));
     lap(3);
     // MapCheckPenalize (:573-595), use_logistic = false
     double penalty = 1.0;
     if (p.use_map_check_feedback) {
+      std::lock_guard<std::mutex> check_lock(f->map_mu);  // :576
       if ((st = csm_gridmap_feedback_penalty(f->maps[CSM_PUB_MAP], f->pub_pts.data(), n, nullptr, pose,
                                              p.map_check_point_num, p.map_check_bound_tolerance,
                                              p.map_check_penalty_gain, 0, &penalty)) != CSM_OK)
@@ -250,6 +258,7 @@ int csm_frontend_process(csm_frontend* f, const double* pts, int32_t n, const do
                            p.map_update_angle_threshold) ||
         !p.use_map_update_move_check)) ||
       f->data_index < 1) {
+    std::lock_guard<std::mutex> map_lock(f->map_mu);  // :533
     csm_gridmap* pub = f->maps[CSM_PUB_MAP];
     if (first)  // :537-542
       st = csm_gridmap_set_cell_params(pub, (float)p.map_min_passthrough, (float)(p.map_min_passthrough * 2), 0.5f,
@@ -330,6 +339,7 @@ int csm_frontend_correct_pose_and_map(csm_frontend* f, int32_t n, const int32_t*
   const int32_t blur[3] = {0, p.coarse_map_use_blur, p.fine_map_use_blur};
   std::vector<double> pts, ps;
   std::vector<int64_t> off;
+  std::lock_guard<std::mutex> map_lock(f->map_mu);  // :346, over the rebuild of all three maps
   for (int k = 0; k < 3; ++k) {
     const size_t use = k == 0 ? pub_ids.size() : (size_t)kept;
     const double factor = 1 / res[k];  // CreateFrom (sensor_data_manager.h:99-115)
@@ -350,6 +360,28 @@ int csm_frontend_correct_pose_and_map(csm_frontend* f, int32_t n, const int32_t*
     if (st != CSM_OK) return f->fail(st, std::string("InitMapWithRangeVec: ") + csm_gridmap_last_error(f->maps[k]));
   }
   return CSM_OK;
+}
+
+int csm_frontend_publish_map(csm_frontend* f, int32_t last_index, csm_occupancy_grid_info* info,
+                             const int8_t** data) {
+  if (!f || !info || !data) return CSM_ERR_INVALID_ARG;
+  std::memset(info, 0, sizeof(*info));
+  *data = nullptr;
+  csm_gridmap* pub = nullptr;
+  {
+    std::lock_guard<std::mutex> map_lock(f->map_mu);  // roborts_slam_node.cpp:364
+    pub = f->maps[CSM_PUB_MAP];
+    info->map_update_index = -1;
+    if (!pub) return CSM_OK;  // occu_grid_map != nullptr (:382)
+    csm_gridmap_state s;
+    int st = csm_gridmap_get_state(pub, &s);
+    if (st != CSM_OK) return st;
+    info->map_update_index = s.map_update_index;
+    if (s.map_update_index == last_index) return CSM_OK;  // :383
+    if ((st = csm_gridmap_occupancy_grid_begin(pub, 0, info)) != CSM_OK) return st;
+  }
+  // the front end goes on; this thread waits for the kernel and the copy
+  return csm_gridmap_occupancy_grid_end(pub, data);
 }
 
 int csm_frontend_last_phases(const csm_frontend* f, double ms[7]) {

@@ -27,6 +27,7 @@
 
 #include "csm_gridmap.h"
 #include "csm_gridmap_internal.hpp"
+#include "csm_gridmap_publish.hpp"
 #include "csm_internal.hpp"
 #include "csm_resources.hpp"
 #include "host_math.hpp"
@@ -120,6 +121,13 @@ struct csm_gridmap {
   csmh::HostBuf h_ends;  // pinned staging of the endpoints (upload_ends)
   bool ktab_dirty = true;
   std::vector<GmEnd> pending;  // blur endpoints not yet drawn (order-free, batched)
+  // The map publisher (csm_gridmap_states, csm_gridmap_occupancy_grid_*): the
+  // states of a box on the device, their pinned host copy, the event after
+  // that copy, and whether a grid was begun and not yet handed out.
+  DevBuf states;
+  csmh::HostBuf h_states;
+  csmh::Event states_done;
+  bool grid_begun = false;
 
   int fail(int code, const std::string& m) {
     err = m;
@@ -589,6 +597,7 @@ int csm_gridmap_create(int device, int32_t kind, double resolution, int32_t size
   DeviceGuard g(device);
   if (m->stream.create(hipStreamNonBlocking) != hipSuccess || m->ready.create(hipEventDisableTiming) != hipSuccess ||
       m->read_done.create(hipEventDisableTiming) != hipSuccess ||
+      m->states_done.create(hipEventDisableTiming) != hipSuccess ||
       m->staged.create(hipEventDisableTiming) != hipSuccess) {
     csm_gridmap_destroy(m);
     return CSM_ERR_HIP;
@@ -895,6 +904,150 @@ int csm_gridmap_device_prob(csm_gridmap* m, const float** p) {
   int st = finish(m);
   if (st != CSM_OK) return st;
   *p = m->prob.as<float>();
+  return CSM_OK;
+}
+
+// ---- the map publisher (roborts_slam_node.cpp:355-488) ------------------------
+
+namespace {
+
+void grid_info(const csm_gridmap* m, bool full_map, csm_occupancy_grid_info* o) {
+  const csm::PublishBox b = full_map
+                                ? csm::publish_full_box(m->size_x, m->size_y)
+                                : csm::publish_box(m->bound.minx, m->bound.miny, m->bound.maxx, m->bound.maxy);
+  csm::publish_origin(m->scale_factor, m->off_x, m->off_y, b.start_x, b.start_y, &o->origin_x, &o->origin_y);
+  o->resolution = csm::publish_resolution(m->scale_factor);
+  o->width = b.width;
+  o->height = b.height;
+  o->start_x = b.start_x;
+  o->start_y = b.start_y;
+  o->map_update_index = m->map_update_index;
+  o->reserved = 0;
+}
+
+// Room for n state bytes on the device (whole dwords) and, with `pinned`, in
+// the host copy. A buffer that grows may still be read by a copy in flight.
+int ensure_states(csm_gridmap* m, int64_t n, bool pinned) {
+  const size_t dev = ((size_t)n + 3) & ~(size_t)3, host = pinned ? (size_t)n : 0;
+  if (dev > m->states.cap || host > m->h_states.cap) GM_HIP(hipStreamSynchronize(m->stream));
+  GM_HIP(m->states.ensure(dev));
+  if (pinned) GM_HIP(m->h_states.ensure(host));
+  return CSM_OK;
+}
+
+bool states_box_ok(int32_t w, int32_t h) { return w >= 0 && h >= 0 && (int64_t)w * h < ((int64_t)1 << 31); }
+
+}  // namespace
+
+int csm_gridmap_states(csm_gridmap* m, int32_t x0, int32_t y0, int32_t w, int32_t h, int8_t* out) {
+  if (!m) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (!states_box_ok(w, h)) return m->fail(CSM_ERR_INVALID_ARG, "states box: negative size or 2^31 cells and more");
+  const int64_t n = (int64_t)w * h;
+  if (n == 0) return CSM_OK;
+  if (!out) return m->fail(CSM_ERR_INVALID_ARG, "states box: null output");
+  DeviceGuard g(m->device);
+  int st;
+  if ((st = flush_pending(m)) != CSM_OK) return st;
+  if ((st = ensure_states(m, n, false)) != CSM_OK) return st;
+  GM_HIP(csm::gm_launch_states(m->cells(), m->ops, x0, y0, w, h, m->states.as<int8_t>(), m->stream));
+  GM_HIP(hipMemcpyAsync(out, m->states.p, (size_t)n, hipMemcpyDeviceToHost, m->stream));
+  GM_HIP(hipStreamSynchronize(m->stream));
+  return CSM_OK;
+}
+
+int csm_gridmap_occupancy_grid_info(csm_gridmap* m, int32_t full_map, csm_occupancy_grid_info* info) {
+  if (!m || !info) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  grid_info(m, full_map != 0, info);
+  return CSM_OK;
+}
+
+int csm_gridmap_occupancy_grid_begin(csm_gridmap* m, int32_t full_map, csm_occupancy_grid_info* info) {
+  if (!m || !info) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  DeviceGuard g(m->device);
+  if (m->grid_begun) GM_HIP(hipEventSynchronize(m->states_done));  // the grid begun before, not handed out yet
+  int st;
+  if ((st = flush_pending(m)) != CSM_OK) return st;
+  grid_info(m, full_map != 0, info);
+  if (!states_box_ok(info->width, info->height))
+    return m->fail(CSM_ERR_INVALID_ARG, "occupancy grid of 2^31 cells and more");
+  const int64_t n = (int64_t)info->width * info->height;
+  if ((st = ensure_states(m, n > 0 ? n : 1, true)) != CSM_OK) return st;
+  if (n > 0) {
+    GM_HIP(csm::gm_launch_states(m->cells(), m->ops, info->start_x, info->start_y, info->width, info->height,
+                                 m->states.as<int8_t>(), m->stream));
+    GM_HIP(hipMemcpyAsync(m->h_states.p, m->states.p, (size_t)n, hipMemcpyDeviceToHost, m->stream));
+  }
+  GM_HIP(hipEventRecord(m->states_done, m->stream));
+  m->grid_begun = true;
+  return CSM_OK;
+}
+
+int csm_gridmap_occupancy_grid_end(csm_gridmap* m, const int8_t** data) {
+  if (!m || !data) return CSM_ERR_INVALID_ARG;
+  *data = nullptr;
+  hipEvent_t done = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (!m->grid_begun) return m->fail(CSM_ERR_INVALID_ARG, "occupancy_grid_end without occupancy_grid_begin");
+    done = m->states_done;
+  }
+  {  // outside the lock: the map's updates go on while the copy lands
+    DeviceGuard g(m->device);
+    const hipError_t e = hipEventSynchronize(done);
+    if (e != hipSuccess) {
+      std::lock_guard<std::mutex> lk(m->mu);
+      return m->hip_fail(e, "hipEventSynchronize(states_done)");
+    }
+  }
+  std::lock_guard<std::mutex> lk(m->mu);
+  m->grid_begun = false;
+  *data = m->h_states.as<int8_t>();
+  return CSM_OK;
+}
+
+int csm_gridmap_occupancy_grid(csm_gridmap* m, int32_t full_map, csm_occupancy_grid_info* info, int8_t* data,
+                               int64_t capacity) {
+  if (!m || !info) return CSM_ERR_INVALID_ARG;
+  int st;
+  if ((st = csm_gridmap_occupancy_grid_begin(m, full_map, info)) != CSM_OK) return st;
+  const int8_t* grid = nullptr;
+  if ((st = csm_gridmap_occupancy_grid_end(m, &grid)) != CSM_OK) return st;
+  const int64_t n = (int64_t)info->width * info->height;
+  if (capacity < n || (n > 0 && !data)) {
+    std::lock_guard<std::mutex> lk(m->mu);
+    return m->fail(CSM_ERR_INVALID_ARG, "occupancy grid: capacity below width * height");
+  }
+  if (n > 0) std::memcpy(data, grid, (size_t)n);
+  return CSM_OK;
+}
+
+int csm_gridmap_occupancy_grid_kernel_ms(csm_gridmap* m, int32_t full_map, int32_t repeats, double* ms) {
+  if (!m || !ms || repeats <= 0) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  DeviceGuard g(m->device);
+  csm_occupancy_grid_info info;
+  int st;
+  if ((st = flush_pending(m)) != CSM_OK) return st;
+  grid_info(m, full_map != 0, &info);
+  const int64_t n = (int64_t)info.width * info.height;
+  if (!states_box_ok(info.width, info.height) || n == 0)
+    return m->fail(CSM_ERR_INVALID_ARG, "occupancy grid empty or of 2^31 cells and more");
+  if ((st = ensure_states(m, n, false)) != CSM_OK) return st;
+  csmh::Event e0, e1;
+  GM_HIP(e0.create(hipEventDefault));
+  GM_HIP(e1.create(hipEventDefault));
+  GM_HIP(hipEventRecord(e0, m->stream));
+  for (int r = 0; r < repeats; ++r)
+    GM_HIP(csm::gm_launch_states(m->cells(), m->ops, info.start_x, info.start_y, info.width, info.height,
+                                 m->states.as<int8_t>(), m->stream));
+  GM_HIP(hipEventRecord(e1, m->stream));
+  GM_HIP(hipEventSynchronize(e1));
+  float total = 0.f;
+  GM_HIP(hipEventElapsedTime(&total, e0, e1));
+  *ms = (double)total / repeats;
   return CSM_OK;
 }
 

@@ -313,6 +313,55 @@ __global__ __launch_bounds__(kThreads) void extend_copy_kernel(GmCells O, GmCell
   }
 }
 
+// GetGridStates of one cell as the map publisher writes it
+// (roborts_slam_node.cpp:405-419, 455-469): 100 occupied, 0 free, -1 unknown.
+// The cell is the reference's GetCell(x, y), linear index y * size_x + x
+// (grid_map_base.h:315-317): a box that ends at GetEndGrid = ceil(max) can
+// name column size_x, which is the next row's first cell. Only a negative x
+// or y, or a linear index past the array (undefined in the reference), is -1.
+__device__ __forceinline__ uint32_t cell_state(const GmCells& C, const GmOps& P, int64_t x, int64_t y,
+                                               int64_t ncells) {
+  if (x < 0 || y < 0) return 0xFFu;
+  const int64_t c = y * C.row + x;
+  if (c >= ncells) return 0xFFu;
+  const float v = C.prob[c];
+  if (P.kind == kGmCount)  // CountCellFunctions::GetGridStates grid_map_cell.h:125-136 (a NaN value: occupied)
+    return C.pass[c] >= P.min_pass ? (v < P.occu_threshold ? 0u : 100u) : 0xFFu;
+  return v < 0.5f ? 0u : (v > 0.5f ? 100u : 0xFFu);  // ProbabilityCellFunctions :367-375
+}
+
+// The states of the box (x0, y0, w, h), row-major into out[h * w]: a lane
+// takes four consecutive output bytes, each with its own (row, column) from
+// the output index (the four may lie in several map rows when w < 4 or at a
+// row end), and stores them as one aligned dword; the lane that holds the last
+// n mod 4 bytes stores them singly. out is 4-byte aligned.
+__global__ __launch_bounds__(kThreads) void states_kernel(GmCells C, GmOps P, int x0, int y0, int w, int64_t n,
+                                                           int8_t* __restrict__ out) {
+  const int64_t ncells = (int64_t)C.row * C.size_y;
+  const int64_t nq = (n + 3) >> 2;
+  for (int64_t q = (int64_t)blockIdx.x * kThreads + threadIdx.x; q < nq; q += (int64_t)gridDim.x * kThreads) {
+    const int64_t k = q << 2;
+    int64_t j = k / w;
+    int i = (int)(k - j * w);
+    uint32_t packed = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      // bytes past n (the last lane's) read no cell
+      const uint32_t s = k + b < n ? cell_state(C, P, (int64_t)x0 + i, (int64_t)y0 + j, ncells) : 0u;
+      packed |= s << (8 * b);
+      if (++i == w) {
+        i = 0;
+        ++j;
+      }
+    }
+    if (k + 4 <= n) {
+      *reinterpret_cast<uint32_t*>(out + k) = packed;
+    } else {
+      for (int b = 0; k + b < n; ++b) out[k + b] = (int8_t)(packed >> (8 * b));
+    }
+  }
+}
+
 unsigned grid_for(int64_t n) {
   int64_t b = (n + kThreads - 1) / kThreads;
   if (b > 8192) b = 8192;
@@ -363,6 +412,14 @@ hipError_t gm_launch_feedback(const GmEnd* ends, int n, int sx, int sy, const Gm
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(feedback_kernel, dim3((unsigned)((n + 3) / 4)), dim3(kThreads), 0, s, ends, n, sx, sy, C, P,
                      use_blur, (float)occu_offset, occu_offset, min_d2, count);
+  return hipGetLastError();
+}
+hipError_t gm_launch_states(const GmCells& C, const GmOps& P, int x0, int y0, int w, int h, int8_t* out,
+                            hipStream_t s) {
+  const int64_t n = (int64_t)w * h;
+  if (w <= 0 || h <= 0) return hipSuccess;
+  if (n >= ((int64_t)1 << 31) || (reinterpret_cast<uintptr_t>(out) & 3u)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(states_kernel, dim3(grid_for((n + 3) >> 2)), dim3(kThreads), 0, s, C, P, x0, y0, w, n, out);
   return hipGetLastError();
 }
 

@@ -55,6 +55,11 @@ hipError_t gm_launch_lines(const GmEnd* ends, int n, int sx, int sy, const GmCel
                            uint64_t* fkey, uint32_t* oseq, uint32_t seq, int tol, hipStream_t s);
 hipError_t gm_launch_feedback(const GmEnd* ends, int n, int sx, int sy, const GmCells& C, const GmOps& P,
                               int use_blur, double occu_offset, int64_t min_d2, int* count, hipStream_t s);
+// GetGridStates (100 / 0 / -1) of the box (x0, y0, w, h), row-major into
+// out[h * w] (device, 4-byte aligned; w * h below 2^31). Cells are read at the
+// linear index y * size_x + x; -1 for a negative x or y or an index past the array.
+hipError_t gm_launch_states(const GmCells& C, const GmOps& P, int x0, int y0, int w, int h, int8_t* out,
+                            hipStream_t s);
 
 // The map's fixed-point mirror for a matcher whose off-grid value is
 // `outside` (gridmap_fixed_point): ok = false when the map's values are not

@@ -45,10 +45,12 @@ EXPORTED = (
     "csm_gridmap_reset", "csm_gridmap_update_bound", "csm_gridmap_update_by_range", "csm_gridmap_init_with_range_vec",
     "csm_gridmap_feedback_penalty", "csm_gridmap_get_state", "csm_gridmap_download",
     "csm_gridmap_device_prob", "csm_set_grid_gridmap", "csm_set_grid_stack_gridmaps",
+    "csm_gridmap_states", "csm_gridmap_occupancy_grid_info", "csm_gridmap_occupancy_grid_begin",
+    "csm_gridmap_occupancy_grid_end", "csm_gridmap_occupancy_grid", "csm_gridmap_occupancy_grid_kernel_ms",
     # include/csm_frontend.h
     "csm_frontend_create", "csm_frontend_destroy", "csm_frontend_last_error", "csm_frontend_process",
     "csm_frontend_map", "csm_frontend_correct_pose_and_map", "csm_frontend_kept_scans", "csm_frontend_matcher",
-    "csm_frontend_last_phases", "csm_frontend_process_ranges",
+    "csm_frontend_last_phases", "csm_frontend_process_ranges", "csm_frontend_publish_map",
     # include/csm_loop_closure.h
     "csm_loop_closure_create", "csm_loop_closure_destroy", "csm_loop_closure_last_error",
     "csm_loop_closure_set_submaps", "csm_loop_closure_match", "csm_loop_closure_match_full",
@@ -250,6 +252,22 @@ class CsmGridmapState(C.Structure):
     ]
 
 
+class CsmOccupancyGridInfo(C.Structure):
+    """csm_occupancy_grid_info (include/csm_gridmap.h)."""
+
+    _fields_ = [
+        ("origin_x", C.c_double),
+        ("origin_y", C.c_double),
+        ("resolution", C.c_double),
+        ("width", C.c_int32),
+        ("height", C.c_int32),
+        ("start_x", C.c_int32),
+        ("start_y", C.c_int32),
+        ("map_update_index", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 _dp = C.POINTER(C.c_double)
 _i64p = C.POINTER(C.c_int64)
 _i32p = C.POINTER(C.c_int32)
@@ -345,6 +363,13 @@ def _bind(lib: C.CDLL) -> C.CDLL:
                                            C.c_void_p]),
         "csm_gridmap_device_prob": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
         "csm_set_grid_gridmap": (C.c_int, [_ctx, C.c_void_p]),
+        "csm_gridmap_states": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+        "csm_gridmap_occupancy_grid_info": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(CsmOccupancyGridInfo)]),
+        "csm_gridmap_occupancy_grid_begin": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(CsmOccupancyGridInfo)]),
+        "csm_gridmap_occupancy_grid_end": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+        "csm_gridmap_occupancy_grid": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(CsmOccupancyGridInfo), C.c_void_p,
+                                                 C.c_int64]),
+        "csm_gridmap_occupancy_grid_kernel_ms": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp]),
         "csm_frontend_create": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
         "csm_frontend_destroy": (C.c_int, [C.c_void_p]),
         "csm_frontend_last_error": (C.c_char_p, [C.c_void_p]),
@@ -355,6 +380,8 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "csm_frontend_last_phases": (C.c_int, [C.c_void_p, _dp]),
         "csm_frontend_correct_pose_and_map": (C.c_int, [C.c_void_p, C.c_int32, _i32p, _dp]),
         "csm_frontend_kept_scans": (C.c_int, [C.c_void_p, _i32p, _dp]),
+        "csm_frontend_publish_map": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(CsmOccupancyGridInfo),
+                                               C.POINTER(C.c_void_p)]),
         "csm_load_scans_grids": (C.c_int, [_ctx, C.c_int32, _dp, _i64p, _i32p]),
         "csm_scan_matchers_batch_grids": (C.c_int, [_ctx, C.c_int32, _dp, _i64p, _i32p, C.POINTER(CsmParam), C.c_int32,
                                                     _dp, _dp, _dp]),

@@ -14,7 +14,7 @@ from dataclasses import dataclass, field, fields
 import numpy as np
 
 from . import _abi
-from .gridmap import OccuGridMap
+from .gridmap import OccuGridMap, _grid_copy
 from .params import SIM_YAML_LEVELS, SIM_YAML_OPTIMIZE, SIM_YAML_OPTIMIZE_FAILED_COST
 
 _lib = _abi.load_library()
@@ -212,6 +212,20 @@ class SlamFrontEnd:
         if st != _abi.CSM_OK:
             raise RuntimeError(f"csm_frontend_correct_pose_and_map: status {st}: "
                                f"{_lib.csm_frontend_last_error(self._h).decode()}")
+
+    def publish_map(self, last_index: int = -1):
+        """csm_frontend_publish_map: (info, grid). grid is None when there is
+        no PubMap yet (info.map_update_index -1) or its map_update_index
+        equals last_index (roborts_slam_node.cpp:382-383); else the int8
+        array [height, width] of the bound box's states, a copy. May run in
+        one thread other than the one that calls process(): ctypes releases
+        the GIL for the call."""
+        info = _abi.CsmOccupancyGridInfo()
+        p = C.c_void_p()
+        st = _lib.csm_frontend_publish_map(self._h, int(last_index), C.byref(info), C.byref(p))
+        if st != _abi.CSM_OK:
+            raise RuntimeError(f"csm_frontend_publish_map: status {st}")
+        return info, (None if not p.value else _grid_copy(p, info))
 
     def kept_poses(self) -> np.ndarray:
         n = C.c_int32(0)

@@ -8,6 +8,8 @@ reads and checks against:
   UpdateMapByRange                         ~ map/occu_grid_map.h:258-329
   InitMapWithRangeVec                      ~ map/occu_grid_map.h:222-255
   MapFeedbackResponsePenalty               ~ map/occu_grid_map.h:331-392
+  GetGridStates / OccupancyGrid            ~ SlamNode::PublishMapThread's cell loop, box and
+                                             origin (roborts_slam_node.cpp:355-488)
 
 Cells live in HBM and every per-cell update is a HIP kernel of
 libroborts_csm.so; this module only moves arrays and fails loudly when the
@@ -20,7 +22,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import COUNT_CELL, PROBABILITY_CELL, CsmGridmapState
+from ._abi import COUNT_CELL, PROBABILITY_CELL, CsmGridmapState, CsmOccupancyGridInfo
 
 _lib = _abi.load_library()
 
@@ -159,10 +161,47 @@ class OccuGridMap:
                                               uidx.ctypes.data, touched.ctypes.data))
         return prob, ps, hit, uidx, touched
 
+    # -- the map publisher (roborts_slam_node.cpp:355-488) ------------------------
+    def GetGridStates(self, x0: int, y0: int, w: int, h: int, out: np.ndarray | None = None) -> np.ndarray:
+        """csm_gridmap_states: GetGridStates of cells (x0 + i, y0 + j) as the
+        int8 array [h, w] (100 occupied, 0 free, -1 unknown); the cell is read
+        at the linear index y * size_x + x. `out`: a C-contiguous int8 buffer
+        of at least h * w bytes to write into (returned as given)."""
+        if out is None:
+            out = np.empty((max(int(h), 0), max(int(w), 0)), dtype=np.int8)
+        elif out.dtype != np.int8 or not out.flags.c_contiguous or out.size < max(int(w), 0) * max(int(h), 0):
+            raise ValueError("out: a C-contiguous int8 array of at least h * w bytes")
+        self._check(_lib.csm_gridmap_states(self._h, int(x0), int(y0), int(w), int(h), out.ctypes.data))
+        return out
+
+    def OccupancyGridInfo(self, full_map: bool = False) -> CsmOccupancyGridInfo:
+        info = CsmOccupancyGridInfo()
+        self._check(_lib.csm_gridmap_occupancy_grid_info(self._h, int(full_map), C.byref(info)))
+        return info
+
+    def OccupancyGrid(self, full_map: bool = False):
+        """(info, int8 array [height, width]): the nav_msgs::OccupancyGrid
+        PublishMapThread fills, for the bound box or (full_map,
+        kDisplayFullMap) the whole map. The array is a copy."""
+        info = CsmOccupancyGridInfo()
+        self._check(_lib.csm_gridmap_occupancy_grid_begin(self._h, int(full_map), C.byref(info)))
+        p = C.c_void_p()
+        self._check(_lib.csm_gridmap_occupancy_grid_end(self._h, C.byref(p)))
+        return info, _grid_copy(p, info)
+
     def device_prob(self) -> int:
         p = C.c_void_p()
         self._check(_lib.csm_gridmap_device_prob(self._h, C.byref(p)))
         return int(p.value or 0)
+
+
+def _grid_copy(p: C.c_void_p, info: CsmOccupancyGridInfo) -> np.ndarray:
+    """The map's pinned buffer (valid until its next grid) as an owned array."""
+    n = info.width * info.height
+    if n == 0:
+        return np.empty((info.height, info.width), dtype=np.int8)
+    buf = (C.c_int8 * n).from_address(p.value)
+    return np.frombuffer(buf, dtype=np.int8).reshape(info.height, info.width).copy()
 
 
 def set_matcher_grid(ctx, m: OccuGridMap):
