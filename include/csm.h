@@ -732,6 +732,63 @@ int csm_list_select(csm_ctx* ctx, const double* score, const int64_t* flat, int6
                     int32_t band_on, double best, int32_t near_on, const double* near_window,
                     int64_t* out_flat, double* out_score, int64_t capacity, int64_t* n_out);
 
+/* --- gated search: every window at or above a response --------------------- */
+/* RangeScanPoseGraph::TryCloseLoop (pose_graph/range_scan_pose_graph.cpp:
+ * 299-355) gates every candidate chain on its own response and links each one
+ * that passes; LinkNearChains (:120-167) does the same. This is that question
+ * for n_windows windows of one scan (windows as csm_search_windows): for every
+ * window whose best score is >= min_response, its argmax as csm_best (ties to
+ * the lowest flat index, as csm_best_window) -- exactly csm_best_windows'
+ * per-window results filtered by score >= min_response, in ascending window
+ * order, without scoring every candidate: one descent of the pooled levels at
+ * the fixed threshold min_response over all windows (the collect's descent),
+ * whose leaves raise a per-window maximum on the device.
+ *
+ * windows_out[k], best_out[k] for k < min(*n_pass, capacity); *n_pass counts
+ * every passing window (csm_search_collect's convention: fewer entries written
+ * than counted is still CSM_OK). capacity == 0 with null arrays only counts;
+ * *n_pass == 0 is CSM_OK. The comparison is on the unclamped score (scores
+ * above 1 exist; the clamp is ScanMatch's, :861-863) and inclusive: a caller
+ * after the reference's strict `>` applies it to best_out[k].score itself.
+ * NaN min_response, n_windows < 1, capacity < 0 or param->type == CSM_FAST:
+ * CSM_ERR_INVALID_ARG.
+ *
+ * The list of leaves that reached their window's running maximum lives in the
+ * collect's device list. When it overflows, the per-window maxima are complete
+ * all the same, so a second descent keeps them and lists only candidates tied
+ * at their window's maximum; if that overflows too (plateaus), automatic
+ * capacity grows the list to the count (deterministic by then) and descends a
+ * third time. CSM_GATE_OVERFLOW -- a fixed list_capacity after the second
+ * overflow, more than 2^26 entries, or an allocation that fails -- and
+ * CSM_GATE_UNPOOLED -- windows outside the pooled search, as
+ * csm_search_stats.exhaustive -- take the exhaustive per-window argmax
+ * filtered on the host: the same bits.
+ * kernel_stats: "pyr_gate" (each descent), "gate_window_best" (launches = the
+ * descents), "search_gated:redescended" and "search_gated:exhaustive"
+ * (launches = the counts). */
+typedef struct csm_gate_options {
+  csm_search_options search;   /* top depth, node capacity, top kernel; probes are off
+                                  (fixed-threshold descent, as the collect) */
+  int64_t list_capacity;       /* 0: automatic (the larger of 10240 and what the context's
+                                  list has grown to; grown once more when ties overflow it);
+                                  > 0: exactly that many entries, never grown */
+} csm_gate_options;
+
+enum csm_gate_path { CSM_GATE_PRUNED = 0, CSM_GATE_OVERFLOW = 1, CSM_GATE_UNPOOLED = 2 };
+
+typedef struct csm_gate_stats {
+  int32_t depth, path, descents, reserved;   /* descents: 1..3 (0 on the fallbacks)    */
+  int64_t candidates;                        /* n_windows * n_cand                     */
+  int64_t listed;                            /* hits counted by the last descent       */
+  int64_t nodes[11];                         /* bounded / scored per level, all descents */
+  double build_ms;                           /* pooled levels built by this call (0: cached) */
+} csm_gate_stats;
+
+int csm_search_gated(csm_ctx* ctx, const double* points_xy, int32_t n_points, const csm_param* param,
+                     int32_t n_windows, const int32_t* grid_index, const double* centers_map,
+                     double min_response, const csm_gate_options* options, int32_t* windows_out,
+                     csm_best* best_out, int32_t capacity, int32_t* n_pass, csm_gate_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

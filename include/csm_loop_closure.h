@@ -98,6 +98,33 @@ int csm_loop_closure_match_full(csm_loop_closure* lc, const double* points_xy, i
                                 const csm_param* param, const double pose_world[3], int32_t search,
                                 double cov[9], csm_loop_closure_result* result, csm_match_result* match);
 
+/* Every submap at or above a response, not only the best: TryCloseLoop
+ * (:299-355) gates each candidate chain on its own response and links every
+ * one that passes, LinkNearChains (:120-167) likewise. Every device runs
+ * csm_search_gated (csm.h) on its shard concurrently; there is no collective:
+ * the answer is per submap and the shards are disjoint contiguous ranges, so
+ * the host concatenates them. results[k], k < min(*n_pass, capacity), in
+ * ascending submap order, each filled as csm_loop_closure_match fills the
+ * winner's (score, global_index, submap, n_devices, x / y / angle, pose_world;
+ * search_ms the concurrent phase, exchange_ms 0); *n_pass counts every submap
+ * whose best score is >= min_response (unclamped, inclusive). The result does
+ * not depend on the device count. capacity == 0 only counts. NaN min_response,
+ * capacity < 0 or param->type == CSM_FAST: CSM_ERR_INVALID_ARG. */
+int csm_loop_closure_match_gated(csm_loop_closure* lc, const double* points_xy, int32_t n_points,
+                                 const csm_param* param, const double pose_world[3], double min_response,
+                                 csm_loop_closure_result* results, int32_t capacity, int32_t* n_pass);
+
+/* csm_loop_closure_match_gated, then for each written entry the full ScanMatch
+ * result of that submap's window, exactly as csm_loop_closure_match_full's
+ * second half (csm_search_match with CSM_COLLECT_AUTO on the device that holds
+ * the submap): matches[k], covs[9k..9k+8] (in/out per entry, as
+ * csm_search_match writes it), results[k].pose_world the averaged pose's world
+ * coordinates. Devices finish in parallel, a device's own submaps in order. */
+int csm_loop_closure_match_gated_full(csm_loop_closure* lc, const double* points_xy, int32_t n_points,
+                                      const csm_param* param, const double pose_world[3], double min_response,
+                                      csm_loop_closure_result* results, int32_t capacity, int32_t* n_pass,
+                                      double* covs, csm_match_result* matches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -457,6 +457,47 @@ int csm_loop_closure_match(csm_loop_closure* lc, const double* pts, int32_t n_po
   return lc_match_locked(lc, pts, n_points, param, pose_world, search, res);
 }
 
+// The device that holds submap `submap`.
+static int lc_owner(const csm_loop_closure* lc, int32_t submap) {
+  const int G = (int)lc->devices.size();
+  int r = 0;
+  while (r < G - 1 && !(submap >= lc->lo[(size_t)r] && submap < lc->hi[(size_t)r])) ++r;
+  return r;
+}
+
+// The full ScanMatch result of res->submap's window, on the device that holds
+// it (csm_search_match on that one window of its resident stack; its pooled
+// levels are the ones the search just used): cov and match as
+// csm_search_match writes them, match->window the submap, res->pose_world the
+// averaged pose's world coordinates. *err: the failure's message (the caller
+// may run several of these at once, one per device).
+static int lc_finish_submap(csm_loop_closure* lc, const double* pts, int32_t n_points, const csm_param* param,
+                            const double pose_world[3], double cov[9], csm_loop_closure_result* res,
+                            csm_match_result* match, std::string* err) {
+  const int r = lc_owner(lc, res->submap);
+  const int32_t local = res->submap - lc->lo[(size_t)r];
+  const double s = 1.0 / lc->resolution;
+  const double tx = s * lc->offsets[2 * (size_t)res->submap], ty = s * lc->offsets[2 * (size_t)res->submap + 1];
+  const double center[3] = {s * pose_world[0] + tx, s * pose_world[1] + ty, pose_world[2]};  // GetMapCoordsPose, as the match
+  DeviceRestore restore;
+  csm_match_options mo{};
+  mo.search.max_depth = -1;  // as null options: the search's own choice
+  mo.collect_capacity = CSM_COLLECT_AUTO;
+  const int st = csm_search_match(lc->ctx[(size_t)r], pts, n_points, param, 1, &local, center, &mo, cov, match);
+  if (st != CSM_OK) {
+    *err = "device " + std::to_string(lc->devices[(size_t)r]) + ": " + csm_last_error(lc->ctx[(size_t)r]);
+    return st;
+  }
+  match->window = res->submap;  // the winner among all submaps
+  // GetWorldCoordsPose of the averaged pose in its submap (grid_map_base.h:83-87)
+  const double inv_a = s * (1.0 / (s * s - 0.0 * 0.0));
+  const double ntx = -(inv_a * tx), nty = -(inv_a * ty);
+  res->pose_world[0] = inv_a * match->pose_map[0] + ntx;
+  res->pose_world[1] = inv_a * match->pose_map[1] + nty;
+  res->pose_world[2] = match->pose_map[2];
+  return CSM_OK;
+}
+
 int csm_loop_closure_match_full(csm_loop_closure* lc, const double* pts, int32_t n_points, const csm_param* param,
                                 const double pose_world[3], int32_t search, double cov[9],
                                 csm_loop_closure_result* res, csm_match_result* match) {
@@ -467,29 +508,130 @@ int csm_loop_closure_match_full(csm_loop_closure* lc, const double* pts, int32_t
   int st = lc_match_locked(lc, pts, n_points, param, pose_world, search, res);
   if (st != CSM_OK) return st;
   if (res->submap < 0) return lc->fail(CSM_ERR_INVALID_ARG, "no submap was scored");
-  // the device that holds the winning submap finishes that one window on its
-  // resident stack (its pooled levels are the ones the search just used)
-  const int G = (int)lc->devices.size();
-  int r = 0;
-  while (r < G - 1 && !(res->submap >= lc->lo[(size_t)r] && res->submap < lc->hi[(size_t)r])) ++r;
-  const int32_t local = res->submap - lc->lo[(size_t)r];
-  const double s = 1.0 / lc->resolution;
-  const double tx = s * lc->offsets[2 * (size_t)res->submap], ty = s * lc->offsets[2 * (size_t)res->submap + 1];
-  const double center[3] = {s * pose_world[0] + tx, s * pose_world[1] + ty, pose_world[2]};  // GetMapCoordsPose, as the match
+  std::string err;
+  if ((st = lc_finish_submap(lc, pts, n_points, param, pose_world, cov, res, match, &err)) != CSM_OK)
+    return lc->fail(st, err);
+  return CSM_OK;
+}
+
+// csm_loop_closure_match_gated with lc->mu held. Every device runs
+// csm_search_gated on its shard concurrently; the answer is per submap and the
+// shards are disjoint contiguous ranges in submap order, so the host
+// concatenates them: no collective.
+static int lc_match_gated_locked(csm_loop_closure* lc, const double* pts, int32_t n_points, const csm_param* param,
+                                 const double pose_world[3], double min_response, csm_loop_closure_result* results,
+                                 int32_t capacity, int32_t* n_pass) {
   DeviceRestore restore;
-  csm_match_options mo{};
-  mo.search.max_depth = -1;  // as null options: the search's own choice
-  mo.collect_capacity = CSM_COLLECT_AUTO;
-  st = csm_search_match(lc->ctx[(size_t)r], pts, n_points, param, 1, &local, center, &mo, cov, match);
-  if (st != CSM_OK)
-    return lc->fail(st, "device " + std::to_string(lc->devices[(size_t)r]) + ": " + csm_last_error(lc->ctx[(size_t)r]));
-  match->window = res->submap;  // the winner among all submaps
-  // GetWorldCoordsPose of the averaged pose in its submap (grid_map_base.h:83-87)
-  const double inv_a = s * (1.0 / (s * s - 0.0 * 0.0));
-  const double ntx = -(inv_a * tx), nty = -(inv_a * ty);
-  res->pose_world[0] = inv_a * match->pose_map[0] + ntx;
-  res->pose_world[1] = inv_a * match->pose_map[1] + nty;
-  res->pose_world[2] = match->pose_map[2];
+  if (lc->n_submaps == 0) return lc->fail(CSM_ERR_NO_GRID, "no submaps set");
+  int32_t na = 0, ns = 0;
+  if (csm_window_dims(param, &na, &ns) != CSM_OK) return lc->fail(CSM_ERR_INVALID_ARG, "invalid window parameters");
+  const int64_t n_cand = (int64_t)na * ns * ns;
+  const int G = (int)lc->devices.size();
+  // GetMapCoordsPose of the query pose in every submap, as lc_match_locked
+  const double s = 1.0 / lc->resolution;
+  std::vector<double> centers(3 * (size_t)lc->n_submaps);
+  for (int32_t i = 0; i < lc->n_submaps; ++i) {
+    centers[3 * (size_t)i] = s * pose_world[0] + s * lc->offsets[2 * (size_t)i];
+    centers[3 * (size_t)i + 1] = s * pose_world[1] + s * lc->offsets[2 * (size_t)i + 1];
+    centers[3 * (size_t)i + 2] = pose_world[2];
+  }
+  using clock = std::chrono::steady_clock;
+  const clock::time_point t_search = clock::now();
+  std::vector<int> status((size_t)G, CSM_OK);
+  std::vector<std::string> errs((size_t)G);
+  std::vector<std::vector<int32_t>> wins((size_t)G);
+  std::vector<std::vector<csm_best>> bests((size_t)G);
+  std::vector<int32_t> counts((size_t)G, 0);
+  auto run = [&](int r) {
+    const int32_t lo = lc->lo[(size_t)r], n = lc->hi[(size_t)r] - lo;
+    if (n <= 0) return;
+    std::vector<int32_t> gi((size_t)n);
+    for (int32_t i = 0; i < n; ++i) gi[(size_t)i] = i;
+    wins[(size_t)r].resize((size_t)n);
+    bests[(size_t)r].resize((size_t)n);
+    const int st = csm_search_gated(lc->ctx[(size_t)r], pts, n_points, param, n, gi.data(),
+                                    centers.data() + 3 * (size_t)lo, min_response, nullptr, wins[(size_t)r].data(),
+                                    bests[(size_t)r].data(), n, &counts[(size_t)r], nullptr);
+    if (st != CSM_OK) {
+      status[(size_t)r] = st;
+      errs[(size_t)r] = csm_last_error(lc->ctx[(size_t)r]);
+    }
+  };
+  if (!lc->workers) lc->workers.reset(new ShardWorkers(G));
+  lc->workers->run(run);
+  for (int r = 0; r < G; ++r)
+    if (status[(size_t)r] != CSM_OK)
+      return lc->fail(status[(size_t)r], "device " + std::to_string(lc->devices[(size_t)r]) + ": " + errs[(size_t)r]);
+  const double search_ms = std::chrono::duration<double, std::milli>(clock::now() - t_search).count();
+  int32_t n = 0;
+  for (int r = 0; r < G; ++r) {
+    for (int32_t k = 0; k < counts[(size_t)r]; ++k, ++n) {
+      if (n >= capacity) continue;
+      const csm_best& b = bests[(size_t)r][(size_t)k];
+      csm_loop_closure_result& res = results[n];
+      res = csm_loop_closure_result{};
+      res.submap = lc->lo[(size_t)r] + wins[(size_t)r][(size_t)k];
+      res.score = b.score;
+      res.global_index = (int64_t)res.submap * n_cand + b.flat_index;
+      res.n_devices = G;
+      res.x = b.x;
+      res.y = b.y;
+      res.angle = b.angle;
+      res.search_ms = search_ms;
+      res.exchange_ms = 0.0;
+      // GetWorldCoordsPose of the candidate in its submap (grid_map_base.h:83-87), as lc_match_locked
+      const double tx = s * lc->offsets[2 * (size_t)res.submap], ty = s * lc->offsets[2 * (size_t)res.submap + 1];
+      const double inv_a = s * (1.0 / (s * s - 0.0 * 0.0));
+      const double ntx = -(inv_a * tx), nty = -(inv_a * ty);
+      res.pose_world[0] = inv_a * res.x + ntx;
+      res.pose_world[1] = inv_a * res.y + nty;
+      res.pose_world[2] = res.angle;
+    }
+  }
+  *n_pass = n;
+  return CSM_OK;
+}
+
+int csm_loop_closure_match_gated(csm_loop_closure* lc, const double* pts, int32_t n_points, const csm_param* param,
+                                 const double pose_world[3], double min_response, csm_loop_closure_result* results,
+                                 int32_t capacity, int32_t* n_pass) {
+  if (!lc || !pts || !param || !pose_world || !n_pass || capacity < 0 || (capacity > 0 && !results) ||
+      !(min_response == min_response))
+    return CSM_ERR_INVALID_ARG;
+  if (param->type == CSM_FAST) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(lc->mu);
+  return lc_match_gated_locked(lc, pts, n_points, param, pose_world, min_response, results, capacity, n_pass);
+}
+
+int csm_loop_closure_match_gated_full(csm_loop_closure* lc, const double* pts, int32_t n_points, const csm_param* param,
+                                      const double pose_world[3], double min_response,
+                                      csm_loop_closure_result* results, int32_t capacity, int32_t* n_pass, double* covs,
+                                      csm_match_result* matches) {
+  if (!lc || !pts || !param || !pose_world || !n_pass || capacity < 0 ||
+      (capacity > 0 && (!results || !covs || !matches)) || !(min_response == min_response))
+    return CSM_ERR_INVALID_ARG;
+  if (param->type == CSM_FAST) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(lc->mu);
+  int st = lc_match_gated_locked(lc, pts, n_points, param, pose_world, min_response, results, capacity, n_pass);
+  if (st != CSM_OK) return st;
+  // each passing submap's device finishes that window: the devices in
+  // parallel, a device's own submaps in order
+  const int G = (int)lc->devices.size();
+  const int32_t m = *n_pass < capacity ? *n_pass : capacity;
+  std::vector<int> status((size_t)G, CSM_OK);
+  std::vector<std::string> errs((size_t)G);
+  auto run = [&](int r) {
+    for (int32_t k = 0; k < m && status[(size_t)r] == CSM_OK; ++k) {
+      if (lc_owner(lc, results[k].submap) != r) continue;
+      status[(size_t)r] = lc_finish_submap(lc, pts, n_points, param, pose_world, covs + 9 * (size_t)k, &results[k],
+                                           &matches[k], &errs[(size_t)r]);
+    }
+  };
+  DeviceRestore restore;
+  if (!lc->workers) lc->workers.reset(new ShardWorkers(G));
+  lc->workers->run(run);
+  for (int r = 0; r < G; ++r)
+    if (status[(size_t)r] != CSM_OK) return lc->fail(status[(size_t)r], errs[(size_t)r]);
   return CSM_OK;
 }
 

@@ -22,6 +22,7 @@
 
 #include "csm_score_sink.hpp"
 #include "csm_pyramid.hpp"
+#include "csm_select.hpp"  // CSM_GATE_MUTATION
 
 #pragma clang fp contract(off)
 
@@ -244,24 +245,20 @@ __global__ __launch_bounds__(kPB) void pyr_bound_kernel(LevelWork L, PyrGrid lev
   block_best(bv, bf, bn, partials + blockIdx.x);
 }
 
-// Collect mode's depth 0 (PyramidSearch::collect): pyr_bound_kernel's exact
-// candidate score at d = 0 -- the same beam staging, gathers, lanes per node
-// and penalised score -- but in place of the block's best every leaf with
-// score >= T is appended to `out` as (score, flat index). A wave's lanes step
-// through the list together (its 64 / lpn nodes per pass), so the append is
-// wave-wide: a ballot of the hits, one returning atomic per wave for their
-// number, each hit's slot from its rank in the ballot. *count takes every hit;
-// only slots below cap are written. Invalid nodes (kPyrNoNode, J or K outside
-// the window) append nothing.
-__global__ __launch_bounds__(kPB) void pyr_collect_kernel(LevelWork L, PyrGrid lev,
-                                                          const ScanWork* __restrict__ scans,
-                                                          const AngleEntry* __restrict__ angles,
-                                                          const double2* __restrict__ pts, int32_t n_used,
-                                                          int32_t step, const uint64_t* __restrict__ nodes,
-                                                          int64_t n_host, const unsigned long long* __restrict__ n_dev,
-                                                          double T, PyrHit* __restrict__ out,
-                                                          unsigned long long* __restrict__ count, int64_t cap,
-                                                          unsigned long long* __restrict__ scored) {
+// Depth 0 of a fixed-threshold descent, shared by pyr_collect_kernel and
+// pyr_gate_kernel: pyr_bound_kernel's exact candidate score at d = 0 -- the
+// same beam staging, gathers, lanes per node and penalised score. A wave's
+// lanes step through the list together (its 64 / lpn nodes per pass), and
+// after each pass every lane of the wave calls leaf(v, flat, w, scored, lane):
+// scored on the one lane per valid node that holds its score v, its global
+// flat index (window * n_cand + flat) and its window w. Invalid nodes
+// (kPyrNoNode, J or K outside the window) are never `scored`.
+template <class Leaf>
+__device__ __forceinline__ void leaf_walk(const LevelWork& L, const PyrGrid& lev, const ScanWork* __restrict__ scans,
+                                          const AngleEntry* __restrict__ angles, const double2* __restrict__ pts,
+                                          int32_t n_used, int32_t step, const uint64_t* __restrict__ nodes,
+                                          int64_t n_host, const unsigned long long* __restrict__ n_dev,
+                                          unsigned long long* __restrict__ scored, Leaf&& leaf) {
   extern __shared__ double2 beams[];
   const int64_t n = n_dev ? (int64_t)*n_dev : n_host;
   const int64_t threads = (int64_t)gridDim.x * kPB;
@@ -315,26 +312,109 @@ __global__ __launch_bounds__(kPB) void pyr_collect_kernel(LevelWork L, PyrGrid l
     for (int o = lpn / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);  // the node's lanes (all valid or none)
     double v = 0.0;
     int64_t flat = 0;
-    bool hit = false;
-    if (valid && sub == 0) {
+    const bool is_leaf = valid && sub == 0;
+    if (is_leaf) {
       const ScanWork S = scans[w];
       const AngleEntry ae = angles[S.angle_off + a];
       const double x = S.x0 + J * L.step_cells;  // :569
       const double y = S.y0 + K * L.step_cells;  // :572
       v = penalized(L, S, dev::fixed_point_acc(L, sum, n_used), x, y, ae.angle);
       flat = (int64_t)w * L.n_cand + ((int64_t)a * L.n_space + J) * L.n_space + K;
-      hit = v >= T;
     }
-    const uint64_t m = __builtin_amdgcn_ballot_w64(hit);
-    if (m == 0) continue;  // uniform
-    unsigned long long first = 0;
-    if (lane == 0) first = atomicAdd(count, (unsigned long long)__builtin_popcountll(m));
-    first = __shfl(first, 0, 64);
-    if (hit) {
-      const int64_t o = (int64_t)first + __builtin_popcountll(m & (((uint64_t)1 << lane) - 1));
-      if (o < cap) out[o] = PyrHit{v, flat};
-    }
+    leaf(v, flat, w, is_leaf, lane);
   }
+}
+
+// The wave-wide append both kernels end a pass with: a ballot of the lanes
+// that append, one returning atomic per wave for their number, each entry's
+// slot from its rank in the ballot. *count takes every one; only slots below
+// cap are written. Called by every lane of the wave.
+__device__ __forceinline__ void wave_append(bool hit, double v, int64_t flat, int lane, PyrHit* __restrict__ out,
+                                            unsigned long long* __restrict__ count, int64_t cap) {
+  const uint64_t m = __builtin_amdgcn_ballot_w64(hit);
+  if (m == 0) return;  // uniform
+  unsigned long long first = 0;
+  if (lane == 0) first = atomicAdd(count, (unsigned long long)__builtin_popcountll(m));
+  first = __shfl(first, 0, 64);
+  if (hit) {
+    const int64_t o = (int64_t)first + __builtin_popcountll(m & (((uint64_t)1 << lane) - 1));
+    if (o < cap) out[o] = PyrHit{v, flat};
+  }
+}
+
+// Collect mode's depth 0 (PyramidSearch::collect): leaf_walk, and in place of
+// pyr_bound_kernel's block best every leaf with score >= T is appended to
+// `out` as (score, flat index) by wave_append.
+__global__ __launch_bounds__(kPB) void pyr_collect_kernel(LevelWork L, PyrGrid lev,
+                                                          const ScanWork* __restrict__ scans,
+                                                          const AngleEntry* __restrict__ angles,
+                                                          const double2* __restrict__ pts, int32_t n_used,
+                                                          int32_t step, const uint64_t* __restrict__ nodes,
+                                                          int64_t n_host, const unsigned long long* __restrict__ n_dev,
+                                                          double T, PyrHit* __restrict__ out,
+                                                          unsigned long long* __restrict__ count, int64_t cap,
+                                                          unsigned long long* __restrict__ scored) {
+  leaf_walk(L, lev, scans, angles, pts, n_used, step, nodes, n_host, n_dev, scored,
+            [&](double v, int64_t flat, int, bool is_leaf, int lane) {
+              wave_append(is_leaf && v >= T, v, flat, lane, out, count, cap);
+            });
+}
+
+// The gated search's depth 0 (PyramidSearch::gate): leaf_walk over the leaves
+// of every window. A leaf with score >= T raises its window's running maximum
+// wkey[w] (select_key's order-preserving image of the score) by a device-scope
+// 64-bit atomicMax, and is appended to the list only if its key is >= the
+// value of wkey[w] it then sees: the list ends up holding every candidate tied
+// at its window's maximum plus whatever was a maximum when it arrived. A stale
+// view of wkey only lengthens the list (keys only rise, equal keys still
+// pass); the keys are complete whether or not the list had room. When every
+// hit lane of the wave is of one window (the usual case: adjacent nodes share
+// a window) the keys are reduced across the wave and one lane issues the one
+// atomic; otherwise each hit lane issues its own. The atomic is skipped when a
+// plain look at wkey[w] already shows a key at least as high.
+__global__ __launch_bounds__(kPB) void pyr_gate_kernel(LevelWork L, PyrGrid lev, const ScanWork* __restrict__ scans,
+                                                       const AngleEntry* __restrict__ angles,
+                                                       const double2* __restrict__ pts, int32_t n_used, int32_t step,
+                                                       const uint64_t* __restrict__ nodes, int64_t n_host,
+                                                       const unsigned long long* __restrict__ n_dev, double T,
+                                                       unsigned long long* __restrict__ wkey, PyrHit* __restrict__ out,
+                                                       unsigned long long* __restrict__ count, int64_t cap,
+                                                       unsigned long long* __restrict__ scored) {
+  // the key a lane sees after raising wkey[w] to at least `key`
+  auto raise = [&](int w, unsigned long long key) -> unsigned long long {
+    unsigned long long cur = __hip_atomic_load(wkey + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (key > cur) {
+      const unsigned long long old = atomicMax(wkey + w, key);
+      cur = old > key ? old : key;
+    }
+    return cur;
+  };
+  leaf_walk(L, lev, scans, angles, pts, n_used, step, nodes, n_host, n_dev, scored,
+            [&](double v, int64_t flat, int w, bool is_leaf, int lane) {
+              const bool hit = is_leaf && v >= T;
+              const uint64_t m = __builtin_amdgcn_ballot_w64(hit);
+              if (m == 0) return;  // uniform
+              const unsigned long long key = hit ? select_key(v) : 0;
+              const int w0 = __shfl(w, __builtin_ctzll(m), 64);
+              unsigned long long seen = 0;
+              if (__builtin_amdgcn_ballot_w64(hit && w != w0) == 0) {  // one window: one atomic for the wave
+                unsigned long long k = key;
+#pragma unroll
+                for (int off = 32; off > 0; off >>= 1) {
+                  const unsigned long long o = __shfl_xor(k, off, 64);
+                  k = o > k ? o : k;
+                }
+                if (lane == 0) seen = raise(w0, k);
+                seen = __shfl(seen, 0, 64);
+              } else if (hit) {
+                seen = raise(w, key);
+              }
+#if CSM_GATE_MUTATION == 2  // the append test made strict must fail the tests
+              wave_append(hit && key > seen, v, flat, lane, out, count, cap);
+#else
+              wave_append(hit && key >= seen, v, flat, lane, out, count, cap);
+#endif
+            });
 }
 
 // The whole top level at once, laid out as the exhaustive column kernel
@@ -952,6 +1032,20 @@ hipError_t launch_pyr_collect(const LevelWork& L, const PyrGrid& lev0, const Sca
   hipLaunchKernelGGL(pyr_collect_kernel, dim3((unsigned)pyr_bound_blocks(upper, n_used)), dim3(kPB),
                      (size_t)n_used * sizeof(double2), stream, L, lev0, scans, angles,
                      reinterpret_cast<const double2*>(pts), n_used, step, nodes, n, n_dev, T, out, count, cap, scored);
+  return hipGetLastError();
+}
+
+hipError_t launch_pyr_gate(const LevelWork& L, const PyrGrid& lev0, const ScanWork* scans, const AngleEntry* angles,
+                           const double* pts, int32_t n_used, int32_t step, const uint64_t* nodes, int64_t n,
+                           const unsigned long long* n_dev, int64_t upper, double T, unsigned long long* wkey,
+                           PyrHit* out, unsigned long long* count, int64_t cap, unsigned long long* scored,
+                           hipStream_t stream) {
+  if (upper <= 0) return hipSuccess;
+  if (lev0.qs != 0 || lev0.lg != 0 || lev0.shift != 0 || !wkey) return hipErrorInvalidValue;  // the fixed-point grid itself
+  hipLaunchKernelGGL(pyr_gate_kernel, dim3((unsigned)pyr_bound_blocks(upper, n_used)), dim3(kPB),
+                     (size_t)n_used * sizeof(double2), stream, L, lev0, scans, angles,
+                     reinterpret_cast<const double2*>(pts), n_used, step, nodes, n, n_dev, T, wkey, out, count, cap,
+                     scored);
   return hipGetLastError();
 }
 

@@ -98,6 +98,17 @@ hipError_t launch_pyr_collect(const LevelWork& L, const PyrGrid& lev0, const Sca
                               const unsigned long long* n_dev, int64_t upper, double T, PyrHit* out,
                               unsigned long long* count, int64_t cap, unsigned long long* scored,
                               hipStream_t stream);
+// The gated search's depth 0 (pyr_gate_kernel): the leaves of every window
+// scored as launch_pyr_collect scores them; a leaf with score >= T raises
+// wkey[window] (select_key of the score, a device-scope atomicMax) and is
+// appended as (score, window * n_cand + flat) only if its key is >= the
+// wkey[window] it then sees. *count takes every appended leaf, only slots
+// below cap are written.
+hipError_t launch_pyr_gate(const LevelWork& L, const PyrGrid& lev0, const ScanWork* scans, const AngleEntry* angles,
+                           const double* pts, int32_t n_used, int32_t step, const uint64_t* nodes, int64_t n,
+                           const unsigned long long* n_dev, int64_t upper, double T, unsigned long long* wkey,
+                           PyrHit* out, unsigned long long* count, int64_t cap, unsigned long long* scored,
+                           hipStream_t stream);
 // The whole top level in one launch (all windows, angles, J, K): nodes and
 // bounds in list order, one best per block (pyr_top_blocks of them; -1 when
 // the grid would not fit a launch).
@@ -221,6 +232,24 @@ class PyramidSearch {
   hipError_t collect_device(const PyrInputs& in, double T, int64_t capacity, int64_t* n_found, PyrStats* stats,
                             std::string* what);
   int64_t list_capacity() const;
+  // The gated search (csm_search_gated): collect's descent at the fixed
+  // threshold T over all in.L.n_scans windows, depth 0 through the windows'
+  // keys (launch_pyr_gate), then the per-window reduction over the list
+  // (launch_gate_window_best); csm_search_gate.hpp says what the state means.
+  // The pooled levels are built here when they are not there (as run builds
+  // them). The list is collect's buffer, `capacity` entries of it;
+  // keep_keys: the keys stay as this context's last gate call left them (the
+  // same windows and T: the descent after an overflow). *out points into
+  // pinned memory that the next gate call rewrites. stats (nullable):
+  // collect_nodes, build_ms and depth. A list that cannot be allocated comes
+  // back as hipErrorOutOfMemory before any of the descent is launched.
+  struct GateOut {
+    const uint64_t* wkey;
+    const int64_t* wflat;
+    int64_t listed;  // entries the descent appended, beyond `capacity` too
+  };
+  hipError_t gate(const PyrInputs& in, double T, int64_t capacity, bool keep_keys, GateOut* out, PyrStats* stats,
+                  std::string* what);
   // The selection of csm_select.hpp over the device list (its count read on
   // the device; n_upper >= it sizes the launches): out[0, min(*n_out, out_cap))
   // in any order (host memory), *n_out the selection's full count. One wait.

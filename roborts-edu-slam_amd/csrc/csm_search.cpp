@@ -76,6 +76,15 @@ struct PyramidSearch::Impl {
   int64_t hit_cap = 0;
   DevBuf hits;
   csmh::HostBuf h_hits;
+  // the gated search (PyramidSearch::gate): collect mode over every window,
+  // depth 0 raising per-window keys (launch_pyr_gate); its device state
+  // (GateHead | wkey | wflat, csm_select.hpp) and the pinned copy of it
+  bool gating = false;
+  DevBuf gate_state;
+  csmh::HostBuf h_gate;
+  csm::GateHead* gate_head() const { return (csm::GateHead*)gate_state.p; }
+  unsigned long long* wkey_dev() const { return (unsigned long long*)(gate_head() + 1); }
+  long long* wflat_dev(int64_t n_windows) const { return (long long*)(wkey_dev() + n_windows); }
   // the selection over the list (csm_select.hpp): its state, its output
   // (count, then entries) and the pinned copy of that output
   DevBuf sel_state, sel_out;
@@ -301,6 +310,10 @@ struct PyramidSearch::Impl {
   hipError_t level_pass(int d, int64_t n, int64_t upper, bool top) {
     hipError_t e;
     const unsigned long long* nd = n >= 0 ? nullptr : count_dev(d);
+    if (collecting && gating && d == 0)  // the same leaves, through their windows' keys
+      return launch_pyr_gate(in.L, lev[0], in.scans, in.angles, in.pts, in.n_used, in.step,
+                             (const uint64_t*)nodes[0].p, n, nd, upper, collect_T, wkey_dev(), (PyrHit*)hits.p,
+                             hits_dev(), hit_cap, scored_dev(), in.stream);
     if (collecting && d == 0)  // the leaves at or above the threshold, appended; nothing to fold
       return launch_pyr_collect(in.L, lev[0], in.scans, in.angles, in.pts, in.n_used, in.step,
                                 (const uint64_t*)nodes[0].p, n, nd, upper, collect_T, (PyrHit*)hits.p, hits_dev(),
@@ -550,6 +563,67 @@ hipError_t PyramidSearch::collect_impl(const PyrInputs& x0, double T, int64_t ca
     stats->collect_nodes[x.depth] += top_scored;
   }
   I.collecting = false;
+  I.st = nullptr;
+  return hipSuccess;
+}
+
+hipError_t PyramidSearch::gate(const PyrInputs& x0, double T, int64_t capacity, bool keep_keys, GateOut* out,
+                               PyrStats* stats, std::string* what) {
+  Impl& I = *p_;
+  auto fail = [&](hipError_t err, const char* msg) {
+    I.collecting = I.gating = false;
+    I.st = nullptr;
+    if (what) *what = msg;
+    return err;
+  };
+  static_assert(kGateLevels == kPyrMaxDepth + 1, "GateHead holds one count per level");
+  const int64_t nw = x0.L.n_scans;
+  if (x0.depth < 0 || x0.depth > kPyrMaxDepth || nw < 1 || capacity < 1 || !out || !(T == T))
+    return fail(hipErrorInvalidValue, "gate: windows, a capacity and a threshold");
+  PyrInputs x = x0;
+  x.timed = 0;
+  PyrStats local;
+  I.st = &local;  // build and build_box note their time there
+  I.in = x;
+  hipError_t e;
+  if ((e = I.build(x)) != hipSuccess) return fail(e, "pyramid levels");
+  const size_t bytes = gate_state_bytes(nw);
+  // a descent that keeps the keys needs the state the last one left
+  if (keep_keys && (!I.gate_state.p || I.gate_state.cap < bytes))
+    return fail(hipErrorInvalidValue, "gate: no keys to keep");
+  if ((e = I.gate_state.ensure_exact(bytes)) != hipSuccess || (e = I.h_gate.ensure_exact(bytes)) != hipSuccess)
+    return fail(e, "gate state");
+  if ((e = I.hits.ensure_exact((size_t)capacity * sizeof(PyrHit))) != hipSuccess) {
+    I.hit_cap = 0;
+    return fail(e, "gate list");
+  }
+  I.collecting = I.gating = true;
+  I.collect_T = T;
+  I.hit_cap = capacity;
+  if ((e = launch_gate_init(I.wkey_dev(), I.wflat_dev(nw), nw, keep_keys && CSM_GATE_MUTATION != 3, x.stream)) !=
+      hipSuccess)
+    return fail(e, "gate_init_kernel");
+  int64_t top_scored = 0;
+  const char* msg = nullptr;
+  if ((e = I.search_levels(x, T, &top_scored, &msg)) != hipSuccess) return fail(e, msg);
+  if ((e = launch_gate_window_best((const PyrHit*)I.hits.p, I.hits_dev(), capacity, x.L.n_cand, I.wkey_dev(),
+                                   I.wflat_dev(nw), I.scored_dev(), I.gate_head(), x.stream)) != hipSuccess)
+    return fail(e, "gate_window_best_kernel");
+  // the keys, the flats, the count and the scored counts: one copy, one wait
+  if ((e = hipMemcpyAsync(I.h_gate.p, I.gate_state.p, bytes, hipMemcpyDeviceToHost, x.stream)) != hipSuccess ||
+      (e = hipStreamSynchronize(x.stream)) != hipSuccess)
+    return fail(e, "gate copy");
+  const GateHead* h = I.h_gate.as<GateHead>();
+  out->wkey = (const uint64_t*)(h + 1);
+  out->wflat = (const int64_t*)(out->wkey + nw);
+  out->listed = (int64_t)h->listed;
+  if (stats) {
+    for (int d = 0; d <= kPyrMaxDepth; ++d) stats->collect_nodes[d] = (int64_t)h->scored[d];
+    stats->collect_nodes[x.depth] += top_scored;
+    stats->build_ms = local.build_ms;
+    stats->depth = x.depth;
+  }
+  I.collecting = I.gating = false;
   I.st = nullptr;
   return hipSuccess;
 }

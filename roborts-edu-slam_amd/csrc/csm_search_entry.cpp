@@ -1,10 +1,11 @@
 // csm_search_entry.cpp — the C-ABI's pooled-search entry points (include/csm.h):
-// csm_search_windows, csm_search_match, and the test hooks csm_search_collect,
+// csm_search_windows, csm_search_match, csm_search_gated, and the test hooks csm_search_collect,
 // csm_search_bounds and csm_list_select, each under staged_call (csm_host.hpp).
 // Here: the plan and the staging they share, the profiling accounts, and
 // csm_search_match's paths. The search itself is PyramidSearch (csm_search.cpp,
 // csm_pyramid.hip), the finish over a collected list csm_search_match.cpp.
 #include "csm_host.hpp"
+#include "csm_search_gate.hpp"
 
 using namespace csmh;
 
@@ -499,9 +500,116 @@ int search_bounds_locked(csm_ctx* c, const double* pts, int32_t n_points, const 
   return CSM_OK;
 }
 
+// One passing window's entry, when there is room for it.
+void gated_put(const SearchPlan& sp, const csm::GatePass& g, int64_t k, int32_t* windows_out, csm_best* best_out) {
+  windows_out[k] = g.window;
+  best_out[k] = best_of(sp.D, sp.plans[(size_t)g.window], sp.angles.data(), sp.f, g.score, g.flat);
+}
+
+// csm_search_gated's fallbacks: the exhaustive per-window argmax, filtered.
+int gated_exhaustive(csm_ctx* c, const csm_param* param, const Geometry& G, const SearchPlan& sp, double T,
+                     int32_t* windows_out, csm_best* best_out, int32_t capacity, int32_t* n_pass) {
+  std::vector<BestPartial> bp(sp.plans.size());
+  std::vector<int64_t> pt_off(sp.plans.size(), 0);
+  int st = run_windows(c, *param, sp.D, G, sp.plans, pt_off, sp.angles.data(), sp.angles.size(), sp.gidx, bp.data());
+  if (st != CSM_OK) return st;
+  int32_t n = 0;
+  for (size_t i = 0; i < bp.size(); ++i) {
+    if (!(bp[i].score >= T)) continue;
+    if (n < capacity) gated_put(sp, csm::GatePass{(int32_t)i, bp[i].score, bp[i].flat}, n, windows_out, best_out);
+    ++n;
+  }
+  *n_pass = n;
+  if (c->profiling) c->account("search_gated:exhaustive", 0.f, 0.0, (double)sp.plans.size() * sp.D.n_cand);
+  return CSM_OK;
+}
+
+// csm_search_gated once locked.
+int search_gated_locked(csm_ctx* c, const double* pts, int32_t n_points, const csm_param* param, int32_t n_windows,
+                        const int32_t* grid_index, const double* centers_map, double T, const csm_gate_options* options,
+                        int32_t* windows_out, csm_best* best_out, int32_t capacity, int32_t* n_pass,
+                        csm_gate_stats* stats) {
+  const Geometry G(c->info);
+  SearchPlan sp;
+  int st = search_plan(c, pts, n_points, param, n_windows, grid_index, centers_map,
+                       options ? options->search.max_depth : -1, G, sp);
+  if (st != CSM_OK) return st;
+  csm_gate_stats S{};
+  S.candidates = (int64_t)n_windows * sp.D.n_cand;
+  auto fallback = [&](int path) {
+    S.path = path;
+    S.descents = 0;
+    if (stats) *stats = S;
+    return gated_exhaustive(c, param, G, sp, T, windows_out, best_out, capacity, n_pass);
+  };
+  if (!sp.ok) return fallback(CSM_GATE_UNPOOLED);
+  csm::PyrInputs in{};
+  if ((st = search_stage(c, param, G, sp, options ? options->search.top_kernel : 0, in)) != CSM_OK) return st;
+  c->pyramid.configure(options ? options->search.node_capacity : 0, -1);  // a fixed threshold: no probes
+  S.depth = sp.depth;
+  const bool fixed = options && options->list_capacity > 0;
+  int64_t cap = csm::gate_first_capacity(options ? options->list_capacity : 0, c->pyramid.list_capacity());
+  if (cap > csm::kGateMaxList) return fallback(CSM_GATE_OVERFLOW);
+  csm::PyramidSearch::GateOut out{};
+  for (int descents = 1;; ++descents) {
+    csm::PyrStats ps;
+    std::string what;
+    hipError_t e;
+    float ms = 0.f;
+    if ((st = c->span_begin("hipEventRecord")) != CSM_OK) return st;
+    if ((e = c->pyramid.gate(in, T, cap, descents > 1, &out, &ps, &what)) != hipSuccess) {
+      if (e != hipErrorOutOfMemory) return c->hip_fail(e, what.c_str());
+      (void)hipGetLastError();  // the list could not be allocated: no error of the context's
+      return fallback(CSM_GATE_OVERFLOW);
+    }
+    if ((st = c->span_end(&ms, "gate timing")) != CSM_OK) return st;
+    int64_t bounded = 0;
+    for (int d = 0; d <= csm::kPyrMaxDepth; ++d) {
+      S.nodes[d] += ps.collect_nodes[d];
+      bounded += ps.collect_nodes[d];
+    }
+    S.build_ms += ps.build_ms;
+    S.listed = out.listed;
+    S.descents = descents;
+    if (c->profiling) {
+      c->account("pyr_gate", ms, (double)bounded * sp.plans[0].n_used * 4.0, (double)S.candidates);
+      c->account("gate_window_best", 0.f, (double)std::min(out.listed, cap) * sizeof(csm::PyrHit), 0.0);
+    }
+    int64_t grow_to = cap;
+    const csm::GateNext next = csm::gate_after(descents, out.listed, cap, fixed, &grow_to);
+    if (next == csm::GateNext::kDone) break;
+    if (next == csm::GateNext::kFallback) return fallback(CSM_GATE_OVERFLOW);
+    if (next == csm::GateNext::kRedescend && c->profiling)
+      c->account("search_gated:redescended", 0.f, 0.0, (double)out.listed);
+    cap = grow_to;
+  }
+  S.path = CSM_GATE_PRUNED;
+  thread_local std::vector<csm::GatePass> pass;
+  if (pass.size() < (size_t)capacity) pass.resize((size_t)capacity);
+  const int64_t n = csm::gate_results(out.wkey, out.wflat, n_windows, sp.D.n_cand, pass.data(), capacity);
+  for (int64_t k = 0; k < std::min<int64_t>(n, capacity); ++k) gated_put(sp, pass[(size_t)k], k, windows_out, best_out);
+  *n_pass = (int32_t)n;
+  if (stats) *stats = S;
+  return CSM_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int csm_search_gated(csm_ctx* c, const double* pts, int32_t n_points, const csm_param* param, int32_t n_windows,
+                     const int32_t* grid_index, const double* centers_map, double min_response,
+                     const csm_gate_options* options, int32_t* windows_out, csm_best* best_out, int32_t capacity,
+                     int32_t* n_pass, csm_gate_stats* stats) {
+  if (!c || !param || !centers_map || !n_pass || n_windows < 1 || capacity < 0 ||
+      (capacity > 0 && (!windows_out || !best_out)) || !(min_response == min_response))
+    return CSM_ERR_INVALID_ARG;
+  if (param->type == CSM_FAST) return c->fail(CSM_ERR_INVALID_ARG, "csm_search_gated: not for the FAST matcher");
+  return staged_call(c, [&] {
+    return search_gated_locked(c, pts, n_points, param, n_windows, grid_index, centers_map, min_response, options,
+                               windows_out, best_out, capacity, n_pass, stats);
+  });
+}
 
 int csm_search_windows(csm_ctx* c, const double* pts, int32_t n_points, const csm_param* param, int32_t n_windows,
                        const int32_t* grid_index, const double* centers_map, const csm_search_options* options,

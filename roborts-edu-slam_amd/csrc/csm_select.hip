@@ -162,7 +162,66 @@ int select_blocks(int64_t upper) {
   return (int)(b < 1 ? 1 : b);
 }
 
+// A gated search's per-window state before a descent: no flat yet; the keys at
+// the lowest key, or kept as the descent before left them (keep_keys).
+__global__ __launch_bounds__(kSB) void gate_init_kernel(unsigned long long* __restrict__ wkey,
+                                                        long long* __restrict__ wflat, int64_t n_windows,
+                                                        int keep_keys) {
+  for (int64_t i = (int64_t)blockIdx.x * kSB + threadIdx.x; i < n_windows; i += (int64_t)gridDim.x * kSB) {
+    if (!keep_keys) wkey[i] = 0;
+    wflat[i] = INT64_MAX;
+  }
+}
+
+// Over the list's first min(*n_dev, cap) entries: an entry whose key equals
+// its window's final key is one of the window's best candidates; the lowest
+// flat among them wins (a 64-bit atomicMin, skipped when a plain look at
+// wflat[w] already shows a lower one: wflat only falls). Thread 0 also copies
+// the descent's counters next to the per-window arrays, so one copy brings
+// everything back.
+__global__ __launch_bounds__(kSB) void gate_window_best_kernel(const PyrHit* __restrict__ hits,
+                                                               const unsigned long long* __restrict__ n_dev,
+                                                               int64_t cap, int64_t n_cand,
+                                                               const unsigned long long* __restrict__ wkey,
+                                                               long long* __restrict__ wflat,
+                                                               const unsigned long long* __restrict__ scored,
+                                                               GateHead* __restrict__ head) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    for (int d = 0; d < kGateLevels; ++d) head->scored[d] = scored[d];
+    head->listed = *n_dev;
+  }
+  const int64_t n = sel_count(n_dev, cap);
+  for (int64_t i = (int64_t)blockIdx.x * kSB + threadIdx.x; i < n; i += (int64_t)gridDim.x * kSB) {
+    const PyrHit x = load_hit(hits, i);
+    const int64_t w = x.flat / n_cand;
+    if (select_key(x.score) != wkey[w]) continue;
+#if CSM_GATE_MUTATION == 1  // a plain store in place of the atomicMin must fail the tests
+    wflat[w] = (long long)x.flat;
+#else
+    if ((long long)x.flat < __hip_atomic_load(wflat + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+      atomicMin(wflat + w, (long long)x.flat);
+#endif
+  }
+}
+
 }  // namespace
+
+hipError_t launch_gate_init(unsigned long long* wkey, long long* wflat, int64_t n_windows, bool keep_keys,
+                            hipStream_t stream) {
+  if (!wkey || !wflat || n_windows < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gate_init_kernel, dim3(select_blocks(n_windows)), dim3(kSB), 0, stream, wkey, wflat, n_windows,
+                     keep_keys ? 1 : 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_gate_window_best(const PyrHit* hits, const unsigned long long* n_dev, int64_t cap, int64_t n_cand,
+                                   const unsigned long long* wkey, long long* wflat, const unsigned long long* scored,
+                                   GateHead* head, hipStream_t stream) {
+  if (!hits || !n_dev || !wkey || !wflat || !scored || !head || cap < 1 || n_cand < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gate_window_best_kernel, dim3(select_blocks(cap)), dim3(kSB), 0, stream, hits, n_dev, cap, n_cand,
+                     wkey, wflat, scored, head);
+  return hipGetLastError();
+}
 
 hipError_t launch_list_select(const PyrHit* hits, const unsigned long long* n_dev, int64_t cap, int64_t upper,
                               const SelectSpec& spec, SelectState* state, SelectHead* out, int64_t out_cap,

@@ -56,4 +56,31 @@ hipError_t launch_list_select(const PyrHit* hits, const unsigned long long* n_de
                               const SelectSpec& spec, SelectState* state, SelectHead* out, int64_t out_cap,
                               hipStream_t stream, int* launches);
 
+// --- the gated search's per-window reduction (PyramidSearch::gate) ----------
+// Device state of a gated search: the head, then wkey[n_windows] (u64: the
+// running maximum of select_key(score) over the window's leaves at or above
+// the gate, raised by pyr_gate_kernel), then wflat[n_windows] (i64: the lowest
+// global flat index among the list's entries whose key equals wkey[w];
+// INT64_MAX: no entry, the window does not pass).
+constexpr int kGateLevels = 11;  // kPyrMaxDepth + 1
+#ifndef CSM_GATE_MUTATION  // the mutation builds of DESIGN 11 (1: plain store for the atomicMin, 2: a strict
+#define CSM_GATE_MUTATION 0  // append test, 3: the keys not kept for the second descent); each must fail tests
+#endif
+struct GateHead {
+  unsigned long long scored[kGateLevels];  // nodes bounded per depth by the last descent
+  unsigned long long listed;               // entries the last descent appended (beyond the list's room too)
+};
+inline size_t gate_state_bytes(int64_t n_windows) { return sizeof(GateHead) + (size_t)n_windows * 16; }
+
+// wflat = INT64_MAX; wkey = 0 unless keep_keys (a second descent keeps them).
+hipError_t launch_gate_init(unsigned long long* wkey, long long* wflat, int64_t n_windows, bool keep_keys,
+                            hipStream_t stream);
+// gate_window_best_kernel over the list's first min(*n_dev, cap) entries
+// (16-byte loads): an entry whose key equals wkey[flat / n_cand] lowers
+// wflat[that window] to its flat (a 64-bit atomicMin). Copies scored[0,
+// kGateLevels) and *n_dev into *head.
+hipError_t launch_gate_window_best(const PyrHit* hits, const unsigned long long* n_dev, int64_t cap, int64_t n_cand,
+                                   const unsigned long long* wkey, long long* wflat, const unsigned long long* scored,
+                                   GateHead* head, hipStream_t stream);
+
 }  // namespace csm

@@ -703,6 +703,43 @@ class Context:
                                           _dptr(cov), C.byref(r)))
         return match_result_dict(r)
 
+    def search_gated(self, points_cells, param, grid_index, centers_map, min_response: float, max_depth: int = -1,
+                     node_capacity: int = 0, top_kernel: int = 0, list_capacity: int = 0,
+                     capacity: int | None = None):
+        """csm_search_gated: every window whose best score is >= min_response,
+        with its argmax -> (windows int32, scores, flat, x, y, angle, n_pass,
+        stats dict): best_windows filtered by score >= min_response, in
+        ascending window order, by one fixed-threshold descent of the pooled
+        levels. At most `capacity` (default: every window) entries come back;
+        n_pass counts every passing window. capacity=0 only counts.
+        list_capacity: 0 = automatic, > 0 = a device list of exactly that
+        many entries. stats: depth, path (_abi.GATE_*), descents, candidates,
+        listed, nodes, build_ms."""
+        pts = np.ascontiguousarray(points_cells, dtype=np.float64).reshape(-1, 2)
+        p = _as_param(param)
+        gi = np.ascontiguousarray(grid_index, dtype=np.int32)
+        ctr = np.ascontiguousarray(centers_map, dtype=np.float64).reshape(-1, 3)
+        assert gi.size == ctr.shape[0]
+        cap = gi.size if capacity is None else int(capacity)
+        opt = _abi.CsmGateOptions(_abi.CsmSearchOptions(int(max_depth), 0, int(node_capacity), int(top_kernel), 0),
+                                  int(list_capacity))
+        wins = np.full(max(cap, 1), -1, dtype=np.int32)
+        out = (CsmBest * max(cap, 1))()
+        n = C.c_int32(-1)
+        st = _abi.CsmGateStats()
+        self._check(_lib.csm_search_gated(self._h, _dptr(pts), pts.shape[0], C.byref(p), gi.size,
+                                          gi.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(ctr), float(min_response),
+                                          C.byref(opt), wins.ctypes.data_as(C.POINTER(C.c_int32)) if cap > 0 else None,
+                                          out if cap > 0 else None, cap, C.byref(n), C.byref(st)))
+        m = min(int(n.value), cap)
+        stats = dict(depth=st.depth, path=st.path, descents=st.descents, candidates=st.candidates, listed=st.listed,
+                     nodes=list(st.nodes), build_ms=st.build_ms)
+        return (wins[:m].copy(), np.array([out[i].score for i in range(m)], dtype=np.float64),
+                np.array([out[i].flat_index for i in range(m)], dtype=np.int64),
+                np.array([out[i].x for i in range(m)], dtype=np.float64),
+                np.array([out[i].y for i in range(m)], dtype=np.float64),
+                np.array([out[i].angle for i in range(m)], dtype=np.float64), int(n.value), stats)
+
     def search_collect(self, points_cells, param, grid_index: int, center_map, depth: int, threshold: float,
                        capacity: int | None = None):
         """csm_search_collect (a test hook): every candidate of one window with

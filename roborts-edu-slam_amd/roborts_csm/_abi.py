@@ -38,7 +38,7 @@ EXPORTED = (
     "csm_optimize_update_cost", "csm_load_scans_grids", "csm_scan_matchers_batch_grids",
     "csm_optimize_scan_match_batch_grids", "csm_scan_matchers_batch_grids_seeded",
     "csm_search_windows", "csm_search_bounds", "csm_host_plan_compute", "csm_get_host_plan",
-    "csm_search_match", "csm_search_collect", "csm_list_select",
+    "csm_search_match", "csm_search_collect", "csm_list_select", "csm_search_gated",
     # include/csm_gridmap.h
     "csm_gridmap_create", "csm_gridmap_destroy", "csm_gridmap_last_error",
     "csm_gridmap_set_options", "csm_gridmap_set_cell_params", "csm_gridmap_set_map_offset",
@@ -54,6 +54,7 @@ EXPORTED = (
     # include/csm_loop_closure.h
     "csm_loop_closure_create", "csm_loop_closure_destroy", "csm_loop_closure_last_error",
     "csm_loop_closure_set_submaps", "csm_loop_closure_match", "csm_loop_closure_match_full",
+    "csm_loop_closure_match_gated", "csm_loop_closure_match_gated_full",
     # include/csm_backend.h
     "csm_backend_create", "csm_backend_destroy", "csm_backend_last_error", "csm_backend_add_scan",
     "csm_backend_set_scan_pose", "csm_backend_scan_match", "csm_backend_map", "csm_backend_matcher",
@@ -168,6 +169,32 @@ class CsmMatchResult(C.Structure):
         ("collected", C.c_int64),
         ("search", CsmSearchStats),
         ("collect_nodes", C.c_int64 * 11),
+    ]
+
+
+class CsmGateOptions(C.Structure):
+    """csm_gate_options (include/csm.h): csm_search_gated."""
+    _fields_ = [
+        ("search", CsmSearchOptions),
+        ("list_capacity", C.c_int64),
+    ]
+
+
+# enum csm_gate_path
+GATE_PRUNED, GATE_OVERFLOW, GATE_UNPOOLED = range(3)
+
+
+class CsmGateStats(C.Structure):
+    """csm_gate_stats (include/csm.h)."""
+    _fields_ = [
+        ("depth", C.c_int32),
+        ("path", C.c_int32),
+        ("descents", C.c_int32),
+        ("reserved", C.c_int32),
+        ("candidates", C.c_int64),
+        ("listed", C.c_int64),
+        ("nodes", C.c_int64 * 11),
+        ("build_ms", C.c_double),
     ]
 
 
@@ -336,6 +363,9 @@ def _bind(lib: C.CDLL) -> C.CDLL:
                                          C.c_double, _i64p, _dp, C.c_int64, _i64p]),
         "csm_list_select": (C.c_int, [_ctx, _dp, _i64p, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_int32, _dp,
                                       _i64p, _dp, C.c_int64, _i64p]),
+        "csm_search_gated": (C.c_int, [_ctx, _dp, C.c_int32, C.POINTER(CsmParam), C.c_int32, _i32p, _dp, C.c_double,
+                                       C.POINTER(CsmGateOptions), _i32p, C.POINTER(CsmBest), C.c_int32, _i32p,
+                                       C.POINTER(CsmGateStats)]),
         "csm_host_plan_compute": (C.c_int, [C.c_int32, C.c_int32, _i32p, C.c_int32, C.POINTER(CsmHostPlan)]),
         "csm_get_host_plan": (C.c_int, [_ctx, C.POINTER(CsmHostPlan)]),
         "csm_optimize_scan_match": (C.c_int, [_ctx, _dp, C.c_int32, C.POINTER(CsmOptimizeParam), _dp, _dp]),
@@ -397,6 +427,11 @@ def _bind(lib: C.CDLL) -> C.CDLL:
                                              C.POINTER(CsmLoopClosureResult)]),
         "csm_loop_closure_match_full": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.POINTER(CsmParam), _dp, C.c_int32, _dp,
                                                   C.POINTER(CsmLoopClosureResult), C.POINTER(CsmMatchResult)]),
+        "csm_loop_closure_match_gated": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.POINTER(CsmParam), _dp, C.c_double,
+                                                   C.POINTER(CsmLoopClosureResult), C.c_int32, _i32p]),
+        "csm_loop_closure_match_gated_full": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.POINTER(CsmParam), _dp,
+                                                        C.c_double, C.POINTER(CsmLoopClosureResult), C.c_int32, _i32p,
+                                                        _dp, C.POINTER(CsmMatchResult)]),
         "csm_backend_create": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
         "csm_backend_destroy": (C.c_int, [C.c_void_p]),
         "csm_backend_last_error": (C.c_char_p, [C.c_void_p]),

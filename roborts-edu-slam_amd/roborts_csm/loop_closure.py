@@ -203,6 +203,52 @@ class DeviceLoopClosure:
         self.last_search_ms, self.last_exchange_ms = float(r.search_ms), float(r.exchange_ms)
         return LoopClosureResult(r.score, r.global_index, r.submap, r.x, r.y, r.angle), match_result_dict(m)
 
+    def _gated(self, points_cells, param, pose_world, min_response, capacity, covs):
+        from . import _as_param, match_result_dict
+        from ._abi import CsmLoopClosureResult, CsmMatchResult
+        C = self._C
+        pts = np.ascontiguousarray(points_cells, dtype=np.float64).reshape(-1, 2)
+        pose = np.ascontiguousarray(pose_world, dtype=np.float64)
+        p = _as_param(param)
+        cap = int(capacity)
+        res = (CsmLoopClosureResult * max(cap, 1))()
+        n = C.c_int32(-1)
+        dp = C.POINTER(C.c_double)
+        head = (self._h, pts.ctypes.data_as(dp), pts.shape[0], C.byref(p), pose.ctypes.data_as(dp),
+                float(min_response), res if cap > 0 else None, cap, C.byref(n))
+        matches = None
+        if covs is None:
+            self._check(self._lib.csm_loop_closure_match_gated(*head))
+        else:
+            assert covs.dtype == np.float64 and covs.flags.c_contiguous and covs.size >= 9 * cap
+            matches = (CsmMatchResult * max(cap, 1))()
+            self._check(self._lib.csm_loop_closure_match_gated_full(*head, covs.ctypes.data_as(dp) if cap > 0 else None,
+                                                                    matches if cap > 0 else None))
+        m = min(int(n.value), cap)
+        self.last_pose_worlds = np.array([res[k].pose_world[:] for k in range(m)]).reshape(m, 3)
+        if m:
+            self.last_n_devices = int(res[0].n_devices)
+            self.last_search_ms, self.last_exchange_ms = float(res[0].search_ms), float(res[0].exchange_ms)
+        out = [LoopClosureResult(res[k].score, res[k].global_index, res[k].submap, res[k].x, res[k].y, res[k].angle)
+               for k in range(m)]
+        return out, int(n.value), ([match_result_dict(matches[k]) for k in range(m)] if matches is not None else None)
+
+    def match_gated(self, points_cells, param, pose_world, min_response: float, capacity: int):
+        """csm_loop_closure_match_gated: every submap whose best score is >=
+        min_response -> (list of LoopClosureResult in ascending submap order,
+        at most `capacity` of them; n_pass, the count of every such submap).
+        last_pose_worlds: the entries' world poses, one row each."""
+        out, n, _ = self._gated(points_cells, param, pose_world, min_response, capacity, None)
+        return out, n
+
+    def match_gated_full(self, points_cells, param, pose_world, min_response: float, capacity: int, covs):
+        """csm_loop_closure_match_gated_full: match_gated, then each entry's
+        full ScanMatch result -> (results, n_pass, list of match dicts as
+        Context.search_match returns them). covs (float64, capacity x 9) is
+        in/out per entry; last_pose_worlds: the averaged poses' world
+        coordinates."""
+        return self._gated(points_cells, param, pose_world, min_response, capacity, covs)
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.csm_loop_closure_destroy(self._h)

@@ -125,13 +125,14 @@ class UseLib:
 
 def load_other(path):
     """Another build of the library, bound with this tree's prototypes. A
-    build older than a hook lacks its symbol: the name gets a stand-in that
-    nothing here calls."""
+    build older than an entry point lacks its symbol: the name gets a stand-in
+    that nothing here calls."""
     import ctypes as C
     from roborts_csm import _abi
     lib = C.CDLL(path)
-    if not hasattr(lib, "csm_list_select"):
-        lib.csm_list_select = lib.csm_abi_version
+    for name in _abi.EXPORTED:  # entry points newer than that build
+        if not hasattr(lib, name):
+            setattr(lib, name, lib.csm_abi_version)
     return _abi._bind(lib)
 
 
