@@ -35,6 +35,7 @@
 #include <stdint.h>
 
 #include "csm.h"
+#include "csm_chain_maps.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -70,6 +71,24 @@ const char* csm_loop_closure_last_error(const csm_loop_closure* lc);
  * i's map_offset_ (m). version as csm_set_grid_stack (unchanged: no upload). */
 int csm_loop_closure_set_submaps(csm_loop_closure* lc, const float* cells, int32_t n_submaps,
                                  const csm_map_info* info, const double* offsets, int64_t version);
+
+/* The submaps drawn on the devices from chains of kept scans
+ * (csm_chain_maps.h) instead of uploaded: what TryCloseLoop and LinkNearChains
+ * need per query, since ScanMatchInterface (slam/slam_processor.cpp:250-326)
+ * rebuilds each chain's map at the poses the pose graph holds at that moment.
+ * add_scan keeps a scan (its end points in metres and its sensor pose) on
+ * every device -- the scans are small, the stores replicated -- and returns
+ * id = 0, 1, ...; set_scan_pose is UpdateRangeData after a graph solve. */
+int csm_loop_closure_add_scan(csm_loop_closure* lc, const double* points_m, int32_t n_points, const double sensor_pose[3], int32_t* id);
+int csm_loop_closure_set_scan_pose(csm_loop_closure* lc, int32_t id, const double sensor_pose[3]);
+/* Submap i = the chain's map centred on current_pose: map_offset = -(current_pose - 0.5 * size * resolution), :452-454
+ * Device r draws only its shard [r*S/G, (r+1)*S/G) (csm_set_grid_stack_chains
+ * on its context), the devices concurrently; every submap's offset is equal,
+ * and the match entry points below run unchanged. Arguments and statuses as
+ * csm_set_grid_stack_chains. A failed call leaves no submaps, as a failed
+ * csm_loop_closure_set_submaps. */
+int csm_loop_closure_set_submaps_chains(csm_loop_closure* lc, const csm_chain_map_param* mp, int32_t n_submaps,
+                                        const int32_t* chain_offsets, const int32_t* chain_ids, const double current_pose[3]);
 
 /* One query: points_xy in map cells (sensor frame, as csm_scan_match), the
  * window param (e.g. +-8 m / +-pi at one-cell steps), pose_world the centre

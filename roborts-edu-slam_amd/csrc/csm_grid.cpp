@@ -333,33 +333,18 @@ void level_work_copies(const csm_ctx* c, ScoreKernel kernel, LevelWork& L) {
   }
 }
 
-}  // namespace csmh
-
-using namespace csmh;
-
-extern "C" {
-
-namespace {
-
 // A grid's size and resolution, and the kernels' 2^31 cell limit.
-int check_grid_size(csm_ctx* c, const csm_map_info* info, const char* what = "grid size and resolution must be positive") {
+int check_grid_size(csm_ctx* c, const csm_map_info* info, const char* what) {
   if (info->size_x <= 0 || info->size_y <= 0 || !(info->resolution > 0.0)) return c->fail(CSM_ERR_INVALID_ARG, what);
   if ((int64_t)info->size_x * info->size_y >= ((int64_t)1 << 31))
     return c->fail(CSM_ERR_INVALID_ARG, "grid larger than 2^31 cells");
   return CSM_OK;
 }
 
-int check_grid_args(csm_ctx* c, const void* cells, int64_t stride, const csm_map_info* info) {
-  if (const int st = check_grid_size(c, info)) return st;
-  if (!cells || stride < 4 || stride % 4 != 0)
-    return c->fail(CSM_ERR_INVALID_ARG, "cells must be non-null with a stride that is a multiple of 4 bytes");
-  return CSM_OK;
-}
-
 // Make n_grids grids at `dev` the current grid, keyed on (cells, stride,
 // version, size); cells = nullptr: no host map's, never found again.
-void adopt_grid(csm_ctx* c, const float* dev, int32_t n_grids, const csm_map_info& info, const void* cells = nullptr,
-                int64_t stride = 0, int64_t version = -1) {
+void adopt_grid(csm_ctx* c, const float* dev, int32_t n_grids, const csm_map_info& info, const void* cells,
+                int64_t stride, int64_t version) {
   c->info = info;
   c->d_grid = dev;
   c->n_grids = n_grids;
@@ -370,6 +355,21 @@ void adopt_grid(csm_ctx* c, const float* dev, int32_t n_grids, const csm_map_inf
   c->key_version = version;
   c->key_sx = info.size_x;
   c->key_sy = info.size_y;
+}
+
+}  // namespace csmh
+
+using namespace csmh;
+
+extern "C" {
+
+namespace {
+
+int check_grid_args(csm_ctx* c, const void* cells, int64_t stride, const csm_map_info* info) {
+  if (const int st = check_grid_size(c, info)) return st;
+  if (!cells || stride < 4 || stride % 4 != 0)
+    return c->fail(CSM_ERR_INVALID_ARG, "cells must be non-null with a stride that is a multiple of 4 bytes");
+  return CSM_OK;
 }
 
 // Whole-grid upload into the current slot (selected by the caller): rows are

@@ -852,6 +852,14 @@ void fill_scan_work_one(const Dims& D, const WindowPlan& W, int64_t pt_off, int3
 // csm_grid.cpp
 int ensure_int_grid(csm_ctx* c);
 void release_map_reader(csm_ctx* c);
+// ... a borrowed device grid or a stack replaces the current grid: the current
+// host-map grid stays parked; a grid's size and resolution and the kernels'
+// 2^31 cell limit; n_grids grids at `dev` made the current grid, keyed on
+// (cells, stride, version, size) (cells = nullptr: no host map's)
+void park_current(csm_ctx* c);
+int check_grid_size(csm_ctx* c, const csm_map_info* info, const char* what = "grid size and resolution must be positive");
+void adopt_grid(csm_ctx* c, const float* dev, int32_t n_grids, const csm_map_info& info, const void* cells = nullptr,
+                int64_t stride = 0, int64_t version = -1);
 
 // csm_grid.cpp: the copies of gridi a level's decision needs (csm_ctx::copies):
 // the palette family where the pair kernel may run, the strips of gridi (and

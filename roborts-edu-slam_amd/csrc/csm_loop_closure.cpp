@@ -162,6 +162,7 @@ struct csm_loop_closure {
   std::string err;
   std::vector<int> devices;
   std::vector<csm_ctx*> ctx;
+  std::vector<csm_scan_store*> stores;  // the kept scans, replicated: one store per device (made by the first add_scan)
   std::vector<ncclComm_t> comms;
   std::vector<hipStream_t> streams;
   std::vector<csm::LcExchange*> xbuf;  // device, one per device
@@ -203,6 +204,8 @@ int csm_loop_closure_destroy(csm_loop_closure* lc) {
   }
   lc->workers.reset();
   if (lc->h_x) (void)hipHostFree(lc->h_x);
+  for (csm_scan_store* st : lc->stores)  // before the contexts: a store waits for the builds that read it
+    if (st) csm_scan_store_destroy(st);
   for (csm_ctx* c : lc->ctx)
     if (c) csm_destroy(c);
   delete lc;
@@ -285,6 +288,111 @@ int csm_loop_closure_set_submaps(csm_loop_closure* lc, const float* cells, int32
   lc->hi.swap(hi);
   lc->resolution = info->resolution;
   lc->offsets.assign(offsets, offsets + 2 * (size_t)n_submaps);
+  lc->n_submaps = n_submaps;
+  return CSM_OK;
+}
+
+// The per-device stores, made on first use.
+static int lc_ensure_stores(csm_loop_closure* lc) {
+  if (!lc->stores.empty()) return CSM_OK;
+  std::vector<csm_scan_store*> made;
+  for (size_t r = 0; r < lc->devices.size(); ++r) {
+    csm_scan_store* st = nullptr;
+    const int rc = csm_scan_store_create(lc->devices[r], &st);
+    if (rc != CSM_OK) {
+      for (csm_scan_store* m : made) csm_scan_store_destroy(m);
+      return lc->fail(rc, "csm_scan_store_create on device " + std::to_string(lc->devices[r]) + " failed");
+    }
+    made.push_back(st);
+  }
+  lc->stores.swap(made);
+  return CSM_OK;
+}
+
+int csm_loop_closure_add_scan(csm_loop_closure* lc, const double* points_m, int32_t n_points, const double sensor_pose[3],
+                              int32_t* id) {
+  if (!lc || !sensor_pose || !id || n_points < 0 || (n_points > 0 && !points_m)) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(lc->mu);
+  DeviceRestore restore;
+  int st;
+  if ((st = lc_ensure_stores(lc)) != CSM_OK) return st;
+  int32_t first = -1;
+  for (size_t r = 0; r < lc->stores.size(); ++r) {
+    int32_t got = -1;
+    if ((st = csm_scan_store_add(lc->stores[r], points_m, n_points, sensor_pose, &got)) != CSM_OK)
+      return lc->fail(st, "device " + std::to_string(lc->devices[r]) + ": " + csm_scan_store_last_error(lc->stores[r]));
+    if (r == 0) first = got;
+    if (got != first) {  // a store an earlier failure left behind the others
+      lc->n_submaps = 0;
+      return lc->fail(CSM_ERR_HIP, "the devices' scan stores are out of step");
+    }
+  }
+  *id = first;
+  return CSM_OK;
+}
+
+int csm_loop_closure_set_scan_pose(csm_loop_closure* lc, int32_t id, const double sensor_pose[3]) {
+  if (!lc || !sensor_pose) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(lc->mu);
+  if (lc->stores.empty()) return lc->fail(CSM_ERR_INVALID_ARG, "no kept scan of that id");
+  for (size_t r = 0; r < lc->stores.size(); ++r) {
+    const int st = csm_scan_store_set_pose(lc->stores[r], id, sensor_pose);
+    if (st != CSM_OK) return lc->fail(st, csm_scan_store_last_error(lc->stores[r]));
+  }
+  return CSM_OK;
+}
+
+int csm_loop_closure_set_submaps_chains(csm_loop_closure* lc, const csm_chain_map_param* mp, int32_t n_submaps,
+                                        const int32_t* chain_offsets, const int32_t* chain_ids,
+                                        const double current_pose[3]) {
+  if (!lc || !mp || !chain_offsets || !current_pose) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(lc->mu);
+  DeviceRestore restore;
+  // as csm_loop_closure_set_submaps: a failed call leaves no submaps
+  lc->n_submaps = 0;
+  if (n_submaps <= 0) return lc->fail(CSM_ERR_INVALID_ARG, "chain maps: n_submaps < 1");
+  if (chain_offsets[0] != 0) return lc->fail(CSM_ERR_INVALID_ARG, "chain maps: chain_offsets[0] must be 0");
+  for (int32_t i = 0; i < n_submaps; ++i)
+    if (chain_offsets[i + 1] < chain_offsets[i])
+      return lc->fail(CSM_ERR_INVALID_ARG, "chain maps: chain_offsets decrease at submap " + std::to_string(i));
+  if (chain_offsets[n_submaps] > 0 && !chain_ids) return lc->fail(CSM_ERR_INVALID_ARG, "chain maps: null chain_ids");
+  int st;
+  if ((st = lc_ensure_stores(lc)) != CSM_OK) return st;
+  // ResetScanMatchMapWithRangeVec (slam_processor.cpp:452-454): the map centred on the current pose
+  const double cell = 1 / (1.0 / mp->resolution);  // GetCellLength()
+  const double map_offset[2] = {-(current_pose[0] - 0.5 * mp->size_x * cell), -(current_pose[1] - 0.5 * mp->size_y * cell)};
+  const int G = (int)lc->devices.size();
+  std::vector<int32_t> lo((size_t)G, 0), hi((size_t)G, 0);
+  for (int r = 0; r < G; ++r) shard_range(n_submaps, r, G, &lo[(size_t)r], &hi[(size_t)r]);
+  // device r draws its shard only, the devices concurrently
+  std::vector<int> status((size_t)G, CSM_OK);
+  std::vector<std::string> errs((size_t)G);
+  auto run = [&](int r) {
+    const int32_t n = hi[(size_t)r] - lo[(size_t)r];
+    if (n == 0) return;
+    const int32_t base = chain_offsets[lo[(size_t)r]];
+    std::vector<int32_t> off((size_t)n + 1);
+    for (int32_t i = 0; i <= n; ++i) off[(size_t)i] = chain_offsets[lo[(size_t)r] + i] - base;
+    const int rc = csm_set_grid_stack_chains(lc->ctx[(size_t)r], lc->stores[(size_t)r], mp, n, off.data(),
+                                             chain_ids ? chain_ids + base : nullptr, map_offset, nullptr);
+    if (rc != CSM_OK) {
+      status[(size_t)r] = rc;
+      errs[(size_t)r] = csm_last_error(lc->ctx[(size_t)r]);
+    }
+  };
+  if (!lc->workers) lc->workers.reset(new ShardWorkers(G));
+  lc->workers->run(run);
+  for (int r = 0; r < G; ++r)
+    if (status[(size_t)r] != CSM_OK)
+      return lc->fail(status[(size_t)r], "device " + std::to_string(lc->devices[(size_t)r]) + ": " + errs[(size_t)r]);
+  lc->lo.swap(lo);
+  lc->hi.swap(hi);
+  lc->resolution = mp->resolution;
+  lc->offsets.resize(2 * (size_t)n_submaps);
+  for (int32_t i = 0; i < n_submaps; ++i) {
+    lc->offsets[2 * (size_t)i] = map_offset[0];
+    lc->offsets[2 * (size_t)i + 1] = map_offset[1];
+  }
   lc->n_submaps = n_submaps;
   return CSM_OK;
 }

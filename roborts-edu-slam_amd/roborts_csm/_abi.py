@@ -55,6 +55,10 @@ EXPORTED = (
     "csm_loop_closure_create", "csm_loop_closure_destroy", "csm_loop_closure_last_error",
     "csm_loop_closure_set_submaps", "csm_loop_closure_match", "csm_loop_closure_match_full",
     "csm_loop_closure_match_gated", "csm_loop_closure_match_gated_full",
+    "csm_loop_closure_add_scan", "csm_loop_closure_set_scan_pose", "csm_loop_closure_set_submaps_chains",
+    # include/csm_chain_maps.h
+    "csm_scan_store_create", "csm_scan_store_destroy", "csm_scan_store_last_error", "csm_scan_store_add",
+    "csm_scan_store_set_pose", "csm_scan_store_count", "csm_set_grid_stack_chains", "csm_grid_download",
     # include/csm_backend.h
     "csm_backend_create", "csm_backend_destroy", "csm_backend_last_error", "csm_backend_add_scan",
     "csm_backend_set_scan_pose", "csm_backend_scan_match", "csm_backend_map", "csm_backend_matcher",
@@ -230,6 +234,21 @@ class CsmLoopClosureResult(C.Structure):
         ("pose_world", C.c_double * 3),
         ("search_ms", C.c_double),
         ("exchange_ms", C.c_double),
+    ]
+
+
+class CsmChainMapParam(C.Structure):
+    """csm_chain_map_param (include/csm_chain_maps.h)."""
+    _fields_ = [
+        ("resolution", C.c_double),
+        ("deviation", C.c_double),
+        ("gaussian_blur_offset", C.c_double),
+        ("size_x", C.c_int32),
+        ("size_y", C.c_int32),
+        ("use_blur", C.c_int32),
+        ("reserved", C.c_int32),
+        ("default_cell_prob", C.c_float),
+        ("reserved_f", C.c_float),
     ]
 
 
@@ -432,6 +451,19 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "csm_loop_closure_match_gated_full": (C.c_int, [C.c_void_p, _dp, C.c_int32, C.POINTER(CsmParam), _dp,
                                                         C.c_double, C.POINTER(CsmLoopClosureResult), C.c_int32, _i32p,
                                                         _dp, C.POINTER(CsmMatchResult)]),
+        "csm_loop_closure_add_scan": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp, _i32p]),
+        "csm_loop_closure_set_scan_pose": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+        "csm_loop_closure_set_submaps_chains": (C.c_int, [C.c_void_p, C.POINTER(CsmChainMapParam), C.c_int32, _i32p,
+                                                          _i32p, _dp]),
+        "csm_scan_store_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+        "csm_scan_store_destroy": (C.c_int, [C.c_void_p]),
+        "csm_scan_store_last_error": (C.c_char_p, [C.c_void_p]),
+        "csm_scan_store_add": (C.c_int, [C.c_void_p, _dp, C.c_int32, _dp, _i32p]),
+        "csm_scan_store_set_pose": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+        "csm_scan_store_count": (C.c_int, [C.c_void_p, _i32p, _i64p]),
+        "csm_set_grid_stack_chains": (C.c_int, [_ctx, C.c_void_p, C.POINTER(CsmChainMapParam), C.c_int32, _i32p, _i32p,
+                                                _dp, C.POINTER(CsmMapInfo)]),
+        "csm_grid_download": (C.c_int, [_ctx, C.c_int32, _f32p, C.c_int64]),
         "csm_backend_create": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
         "csm_backend_destroy": (C.c_int, [C.c_void_p]),
         "csm_backend_last_error": (C.c_char_p, [C.c_void_p]),

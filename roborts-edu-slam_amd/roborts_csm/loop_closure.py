@@ -164,6 +164,42 @@ class DeviceLoopClosure:
                                                            C.byref(info), off.ctypes.data_as(C.POINTER(C.c_double)),
                                                            int(version)))
 
+    def add_scan(self, points_m, sensor_pose) -> int:
+        """csm_loop_closure_add_scan: keep a scan (sensor-frame end points in
+        metres, its sensor pose) on every device -> its id (0, 1, ...)."""
+        C = self._C
+        pts = np.ascontiguousarray(points_m, dtype=np.float64).reshape(-1, 2)
+        pose = np.ascontiguousarray(sensor_pose, dtype=np.float64)
+        assert pose.size == 3
+        dp = C.POINTER(C.c_double)
+        i = C.c_int32(-1)
+        self._check(self._lib.csm_loop_closure_add_scan(self._h, pts.ctypes.data_as(dp), pts.shape[0],
+                                                        pose.ctypes.data_as(dp), C.byref(i)))
+        return int(i.value)
+
+    def set_scan_pose(self, scan_id: int, sensor_pose):
+        """csm_loop_closure_set_scan_pose: UpdateRangeData after a graph solve."""
+        C = self._C
+        pose = np.ascontiguousarray(sensor_pose, dtype=np.float64)
+        assert pose.size == 3
+        self._check(self._lib.csm_loop_closure_set_scan_pose(self._h, int(scan_id),
+                                                             pose.ctypes.data_as(C.POINTER(C.c_double))))
+
+    def set_submaps_chains(self, param, chains, current_pose):
+        """csm_loop_closure_set_submaps_chains: submap i drawn on its device
+        from the kept scans chains[i] (ids) at their stored poses, centred on
+        current_pose. param: chain_maps.ChainMapParam."""
+        from .chain_maps import _chain_arrays
+        C = self._C
+        off, ids = _chain_arrays(chains)
+        pose = np.ascontiguousarray(current_pose, dtype=np.float64)
+        assert pose.size == 3
+        mp = param.to_c()
+        i32p = C.POINTER(C.c_int32)
+        self._check(self._lib.csm_loop_closure_set_submaps_chains(self._h, C.byref(mp), off.size - 1,
+                                                                  off.ctypes.data_as(i32p), ids.ctypes.data_as(i32p),
+                                                                  pose.ctypes.data_as(C.POINTER(C.c_double))))
+
     def match(self, points_cells, param, pose_world, search: str = "pyramid") -> LoopClosureResult:
         from . import _as_param
         from ._abi import CsmLoopClosureResult
