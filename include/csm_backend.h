@@ -97,7 +97,12 @@ int csm_backend_add_scan(csm_backend* be, const double* points_m, int32_t n_poin
 int csm_backend_set_scan_pose(csm_backend* be, int32_t id, const double sensor_pose[3]);
 /* n_jobs ScanMatchInterface calls. current_pose = current_sensor_pose_ (the
  * back-end maps are centred on it); pub_map = the PubMap of the map check
- * (CountCell; null skips the check, penalty 1). */
+ * (CountCell; null skips the check, penalty 1). All jobs are checked by one
+ * csm_gridmap_feedback_penalty_batch (csm_map_check.h), which scales the raw
+ * points by pub_map's own 1 / resolution: a pub_map whose resolution is not
+ * param.map_resolution, and map_check_point_num == 1 with a job of two points
+ * or more (the reference divides by zero, occu_grid_map.h:368), are
+ * CSM_ERR_INVALID_ARG. */
 int csm_backend_scan_match(csm_backend* be, csm_gridmap* pub_map, const double current_pose[3],
                            csm_backend_job* jobs, int32_t n_jobs);
 /* Borrow map pair `slot` (which: 0 coarse, 1 fine); null before first use. */

@@ -36,6 +36,7 @@
 
 #include "csm.h"
 #include "csm_chain_maps.h"
+#include "csm_map_check.h"
 
 #ifdef __cplusplus
 extern "C" {
@@ -143,6 +144,19 @@ int csm_loop_closure_match_gated_full(csm_loop_closure* lc, const double* points
                                       const csm_param* param, const double pose_world[3], double min_response,
                                       csm_loop_closure_result* results, int32_t capacity, int32_t* n_pass,
                                       double* covs, csm_match_result* matches);
+
+/* The reference's gate on a gated result: TryCloseLoop and LinkNearChains compare
+ * response * MapCheckPenalize(pub range data, best_pose, true), clamped to 1
+ * (slam/slam_processor.cpp:312-317, :573-595; range_scan_pose_graph.cpp:159,322,333).
+ * penalties[k] = that penalty of the kept scan scan_id at results[k].pose_world, k < n,
+ * on pub_map: csm_gridmap_feedback_penalty_store (csm_map_check.h) over this handle's
+ * store on pub_map's device, one launch for all n. Only penalties is written: the
+ * loop-closure window is one wide level, not the reference's three, so the score it
+ * would multiply is the caller's to choose. CSM_ERR_INVALID_ARG when none of the
+ * handle's devices is the map's, or scan_id is no kept scan. */
+int csm_loop_closure_map_check(csm_loop_closure* lc, csm_gridmap* pub_map, int32_t scan_id,
+                               const csm_map_check_param* param, const csm_loop_closure_result* results,
+                               int32_t n, double* penalties);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,7 @@
 #include "csm.h"
 #include "csm_backend.h"
 #include "csm_gridmap.h"
+#include "csm_map_check.h"
 #include "csm_matchers.hpp"
 
 namespace {
@@ -270,16 +271,26 @@ int csm_backend_scan_match(csm_backend* b, csm_gridmap* pub, const double cur[3]
     }
   }
   // MapCheckPenalize(pub range data, best_pose, use_logistic = true) (:315-317, :573-595)
-  for (int32_t j = 0; j < n_jobs && pub && p.use_map_check_feedback; ++j) {
-    csm_backend_job& jb = jobs[j];
-    std::vector<double> pp;
-    scale_points(jb.points_m, jb.n_points, 1 / p.map_resolution, pp);
-    double penalty = 1.0;
-    if ((st = csm_gridmap_feedback_penalty(pub, pp.data(), jb.n_points, nullptr, jb.pose, p.map_check_point_num,
-                                           p.map_check_bound_tolerance, p.map_check_penalty_gain, 0, &penalty)) !=
-        CSM_OK)
-      return b->fail(st, "MapFeedbackResponsePenalty");
-    jb.map_penalty = (1 / (1 + std::exp(-10 * (penalty - 0.4))));
+  // for all jobs in one launch: the pub range data is CreateFrom(raw, 1 / map_resolution) (:268-272),
+  // the PubMap's own scale, which csm_gridmap_feedback_penalty_batch applies to the raw points on the device
+  if (n_jobs > 0 && pub && p.use_map_check_feedback) {
+    csm_gridmap_state ps{};
+    if ((st = csm_gridmap_get_state(pub, &ps)) != CSM_OK) return b->fail(st, "csm_gridmap_get_state(pub map)");
+    if (ps.scale_factor != 1 / p.map_resolution)
+      return b->fail(CSM_ERR_INVALID_ARG, "the pub map's resolution is not the back end's map_resolution");
+    std::vector<double> pts, poses((size_t)n_jobs * 3), penalty((size_t)n_jobs, 1.0);
+    std::vector<int64_t> off(1, 0);
+    for (int32_t j = 0; j < n_jobs; ++j) {
+      pts.insert(pts.end(), jobs[j].points_m, jobs[j].points_m + 2 * (size_t)jobs[j].n_points);
+      off.push_back(off.back() + jobs[j].n_points);
+      std::memcpy(&poses[(size_t)3 * j], jobs[j].pose, sizeof(double) * 3);
+    }
+    const csm_map_check_param mc{p.map_check_point_num, 0, 1, 0, p.map_check_bound_tolerance,
+                                 p.map_check_penalty_gain};
+    if ((st = csm_gridmap_feedback_penalty_batch(pub, n_jobs, pts.data(), off.data(), n_jobs, nullptr, poses.data(),
+                                                 &mc, penalty.data(), nullptr)) != CSM_OK)
+      return b->fail(st, std::string("MapFeedbackResponsePenalty: ") + csm_gridmap_last_error(pub));
+    for (int32_t j = 0; j < n_jobs; ++j) jobs[j].map_penalty = penalty[(size_t)j];
   }
   for (int32_t j = 0; j < n_jobs; ++j) {
     jobs[j].score *= jobs[j].map_penalty;  // :318-319

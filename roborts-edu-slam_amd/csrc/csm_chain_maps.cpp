@@ -41,6 +41,15 @@ struct csm_scan_store {
   }
 };
 
+std::unique_lock<std::mutex> csm::scan_store_lock(csm_scan_store* s, csm::ScanStoreView* v) {
+  std::unique_lock<std::mutex> lk(s->mu);
+  v->device = s->device;
+  v->pts = (const double*)s->pts.p;
+  v->scans = s->scans.data();
+  v->n_scans = (int32_t)s->scans.size();
+  return lk;
+}
+
 extern "C" {
 
 int csm_scan_store_create(int device, csm_scan_store** out) {

@@ -19,6 +19,7 @@
 
 #include <cmath>
 #include <cstdint>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -34,6 +35,19 @@ struct ChainScan {
   int32_t n_points = 0;
   double pose[3] = {0.0, 0.0, 0.0};
 };
+
+// A store as another unit reads it in place (the map check, csm_gridmap.cpp):
+// its device, its points buffer (x, y in metres, back to back) and its scans.
+struct ScanStoreView {
+  int device = 0;
+  const double* pts = nullptr;
+  const ChainScan* scans = nullptr;
+  int32_t n_scans = 0;
+};
+// Locks the store and fills the view, valid while the returned lock lives: no
+// scan is added and the buffer is not replaced meanwhile, so a reader that
+// drains its stream before it lets go never outlives the buffer.
+std::unique_lock<std::mutex> scan_store_lock(csm_scan_store* s, ScanStoreView* v);
 
 // One scan drawn into one grid. 48 bytes, read by the splat kernel as it is.
 struct ChainPlacement {

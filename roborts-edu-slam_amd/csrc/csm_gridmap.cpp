@@ -25,10 +25,13 @@
 #include <utility>
 #include <vector>
 
+#include "csm_chain_maps.hpp"
 #include "csm_gridmap.h"
 #include "csm_gridmap_internal.hpp"
 #include "csm_gridmap_publish.hpp"
 #include "csm_internal.hpp"
+#include "csm_map_check.h"
+#include "csm_map_check_plan.hpp"
 #include "csm_resources.hpp"
 #include "host_math.hpp"
 
@@ -128,6 +131,13 @@ struct csm_gridmap {
   csmh::HostBuf h_states;
   csmh::Event states_done;
   bool grid_begun = false;
+  // The batched map check (csm_map_check.h): a call's pose records, then the
+  // points they index (the host form), staged and on the device; the counts
+  // there and back. Every call drains the stream before it returns, so each
+  // buffer is free when the next call begins. Grown, never shrunk.
+  csmh::HostBuf h_check, h_check_counts;
+  DevBuf check, check_counts;
+  int64_t check_launches = 0;
 
   int fail(int code, const std::string& m) {
     err = m;
@@ -792,8 +802,8 @@ int csm_gridmap_feedback_penalty(csm_gridmap* m, const double* pts, int32_t n, c
   if (!m || !best_pose || !coeff || n < 0 || (n > 0 && !pts)) return CSM_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(m->mu);
   DeviceGuard g(m->device);
-  // MapFeedbackResponsePenalty (occu_grid_map.h:331-392)
-  if (bound_tolerance < 0 || check_point_num <= 0 || penalty_gain <= 0.0 || penalty_gain >= 1.0) {
+  // MapFeedbackResponsePenalty (occu_grid_map.h:331-392); the rules are csm_map_check_plan.hpp's
+  if (csm::map_check_guard(check_point_num, bound_tolerance, penalty_gain)) {
     *coeff = 1.0;
     return CSM_OK;
   }
@@ -823,14 +833,7 @@ int csm_gridmap_feedback_penalty(csm_gridmap* m, const double* pts, int32_t n, c
     if ((x0 == x1 && y0 == y1) || !point_in_map(m, x1, y1)) continue;
     rays.push_back(GmEnd{x1, y1, 0, 0});
   }
-  // smallest integer d2 with sqrt(d2) > bound_tolerance (util::EuclideanDistance2d,
-  // slam_util.h:94-96; sqrt is monotonic, so the test is d2 >= min_d2)
-  int64_t min_d2 = INT64_MAX;  // NaN or huge tolerance: no cell is ever far enough
-  if (bound_tolerance < 1e9) {
-    const double t0 = std::floor(bound_tolerance * bound_tolerance) - 2.0;
-    min_d2 = t0 > 0.0 ? (int64_t)t0 : 0;
-    while (!(std::sqrt((double)min_d2) > bound_tolerance)) ++min_d2;
-  }
+  const int64_t min_d2 = csm::map_check_min_d2(bound_tolerance);
   int st;
   if ((st = flush_pending(m)) != CSM_OK) return st;
   int count = 0;
@@ -842,10 +845,217 @@ int csm_gridmap_feedback_penalty(csm_gridmap* m, const double* pts, int32_t n, c
     GM_HIP(hipMemcpyAsync(&count, m->count.p, 4, hipMemcpyDeviceToHost, m->stream));
     GM_HIP(hipStreamSynchronize(m->stream));
   }
-  double penalty = 0;
-  for (int i = 0; i < count; ++i) penalty += 1.0;
-  penalty *= penalty_gain;
-  *coeff = std::max((1.0 + 2 * penalty_gain - penalty), 0.1);
+  *coeff = csm::map_check_coeff(count, penalty_gain);
+  return CSM_OK;
+}
+
+// ---- the batched map check (csm_map_check.h) ----------------------------------
+
+namespace {
+
+using csm::MapCheckPose;
+
+double check_result(const csm_map_check_param& p, double penalty) {  // MapCheckPenalize :589-591
+  return p.use_logistic ? csm::map_check_logistic(penalty) : penalty;
+}
+
+// Pinned room for a call's n_poses records and pts_bytes of points behind them.
+int check_stage(csm_gridmap* m, int32_t n_poses, size_t pts_bytes) {
+  GM_HIP(m->h_check.ensure((size_t)n_poses * sizeof(MapCheckPose) + pts_bytes));
+  GM_HIP(m->h_check_counts.ensure((size_t)n_poses * 4));
+  return CSM_OK;
+}
+
+// The staged records (and pts_bytes of points behind them) go up in one copy.
+int check_upload(csm_gridmap* m, int32_t n_poses, size_t pts_bytes) {
+  int st;
+  if ((st = flush_pending(m)) != CSM_OK) return st;
+  const size_t up_bytes = (size_t)n_poses * sizeof(MapCheckPose) + pts_bytes;
+  if (up_bytes > m->check.cap || (size_t)n_poses * 4 > m->check_counts.cap) GM_HIP(hipStreamSynchronize(m->stream));
+  GM_HIP(m->check.ensure(up_bytes));
+  GM_HIP(m->check_counts.ensure((size_t)n_poses * 4));
+  GM_HIP(hipMemcpyAsync(m->check.p, m->h_check.p, up_bytes, hipMemcpyHostToDevice, m->stream));
+  return CSM_OK;
+}
+
+// The kernel over the uploaded records. dev_pts: the points the records index
+// when they are resident already (null: the ones uploaded behind the records).
+hipError_t check_launch(csm_gridmap* m, int32_t n_poses, const double* dev_pts, const csm_map_check_param& p) {
+  const double* pts = dev_pts ? dev_pts : (const double*)(m->check.as<MapCheckPose>() + n_poses);
+  return csm::gm_launch_feedback_batch(m->check.as<MapCheckPose>(), n_poses, pts, m->scale_factor, m->cells(), m->ops,
+                                       p.use_blur ? 1 : 0, m->occu_offset, csm::map_check_min_d2(p.bound_tolerance),
+                                       m->check_counts.as<int>(), m->stream);
+}
+
+// One upload, one launch, the counts back, one synchronise.
+int check_run(csm_gridmap* m, int32_t n_poses, size_t pts_bytes, const double* dev_pts, const csm_map_check_param& p) {
+  int st;
+  if ((st = check_upload(m, n_poses, pts_bytes)) != CSM_OK) return st;
+  GM_HIP(check_launch(m, n_poses, dev_pts, p));
+  ++m->check_launches;
+  GM_HIP(hipMemcpyAsync(m->h_check_counts.p, m->check_counts.p, (size_t)n_poses * 4, hipMemcpyDeviceToHost,
+                        m->stream));
+  GM_HIP(hipStreamSynchronize(m->stream));
+  return CSM_OK;
+}
+
+// The penalties from the counts that came back (:388-391), 0.0 for a pose outside the map (:351-354).
+void check_finish(const csm_gridmap* m, int32_t n_poses, const csm_map_check_param& p, double* coeff,
+                  int32_t* counts) {
+  const MapCheckPose* rec = m->h_check.as<MapCheckPose>();
+  const int32_t* got = m->h_check_counts.as<int32_t>();
+  for (int32_t k = 0; k < n_poses; ++k) {
+    const bool outside = rec[k].no_rays != 0;
+    coeff[k] = check_result(p, outside ? 0.0 : csm::map_check_coeff(got[k], p.penalty_gain));
+    if (counts) counts[k] = outside ? -1 : got[k];
+  }
+}
+
+void check_guarded(int32_t n_poses, const csm_map_check_param& p, double* coeff, int32_t* counts) {
+  for (int32_t k = 0; k < n_poses; ++k) {
+    coeff[k] = check_result(p, 1.0);
+    if (counts) counts[k] = 0;
+  }
+}
+
+// The store form's records, staged: pose k over the kept scan scan_ids[k], read
+// in place with the scan's own step. Under the map's and the store's locks.
+int check_store_records(csm_gridmap* m, const csm::ScanStoreView& v, int32_t n_poses, const int32_t* scan_ids,
+                        const double* poses, const csm_map_check_param& p) {
+  if (v.device != m->device) return m->fail(CSM_ERR_INVALID_ARG, "map check: the scan store lives on another device");
+  for (int32_t k = 0; k < n_poses; ++k) {
+    if (scan_ids[k] < 0 || scan_ids[k] >= v.n_scans)
+      return m->fail(CSM_ERR_INVALID_ARG, "map check: scan_ids[" + std::to_string(k) + "] is no kept scan of the store");
+    if (csm::map_check_divides_by_zero(p.check_point_num, v.scans[scan_ids[k]].n_points))
+      return m->fail(CSM_ERR_INVALID_ARG, "map check: check_point_num == 1 with a scan of two points or more");
+  }
+  int st;
+  if ((st = check_stage(m, n_poses, 0)) != CSM_OK) return st;
+  MapCheckPose* rec = m->h_check.as<MapCheckPose>();
+  for (int32_t k = 0; k < n_poses; ++k) {
+    const csm::ChainScan& sc = v.scans[scan_ids[k]];
+    csm::map_check_pose(m->scale_factor, m->off_x, m->off_y, m->size_x, m->size_y, poses + 3 * (size_t)k, &rec[k]);
+    rec[k].pt_begin = sc.pt_begin;
+    rec[k].step = csm::map_check_step(sc.n_points, p.check_point_num);
+    rec[k].n_checked = csm::map_check_checked(sc.n_points, rec[k].step);
+  }
+  return CSM_OK;
+}
+
+}  // namespace
+
+int csm_gridmap_feedback_penalty_batch(csm_gridmap* m, int32_t n_scans, const double* points_m,
+                                       const int64_t* point_offsets, int32_t n_poses, const int32_t* scan_index,
+                                       const double* poses, const csm_map_check_param* p, double* coeff,
+                                       int32_t* counts) {
+  if (!m || !p || n_scans < 0 || n_poses < 0 || (n_scans > 0 && !point_offsets) ||
+      (n_poses > 0 && (!poses || !coeff)) || (!scan_index && n_poses != n_scans))
+    return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (n_poses == 0) return CSM_OK;
+  if (csm::map_check_guard(p->check_point_num, p->bound_tolerance, p->penalty_gain)) {
+    check_guarded(n_poses, *p, coeff, counts);
+    return CSM_OK;
+  }
+  for (int32_t i = 0; i < n_scans; ++i) {
+    const int64_t len = point_offsets[i + 1] - point_offsets[i];
+    if (point_offsets[i] < 0 || len < 0 || len > INT32_MAX || (len > 0 && !points_m))
+      return m->fail(CSM_ERR_INVALID_ARG, "map check: point_offsets decrease, or a scan of 2^31 points and more");
+  }
+  // each checked scan's checked points once, in the order the poses first name them
+  std::vector<int64_t> at((size_t)n_scans, -1);  // where a scan's checked points start in the staging, in points
+  int64_t n_up = 0;
+  for (int32_t k = 0; k < n_poses; ++k) {
+    const int32_t i = scan_index ? scan_index[k] : k;
+    if (i < 0 || i >= n_scans)
+      return m->fail(CSM_ERR_INVALID_ARG, "map check: scan_index[" + std::to_string(k) + "] is no scan of the call");
+    if (at[(size_t)i] >= 0) continue;
+    const int32_t n = (int32_t)(point_offsets[i + 1] - point_offsets[i]);
+    if (csm::map_check_divides_by_zero(p->check_point_num, n))
+      return m->fail(CSM_ERR_INVALID_ARG, "map check: check_point_num == 1 with a scan of two points or more");
+    at[(size_t)i] = n_up;
+    n_up += csm::map_check_checked(n, csm::map_check_step(n, p->check_point_num));
+  }
+  DeviceGuard g(m->device);
+  int st;
+  if ((st = check_stage(m, n_poses, (size_t)n_up * 16)) != CSM_OK) return st;
+  MapCheckPose* rec = m->h_check.as<MapCheckPose>();
+  double* up = (double*)(rec + n_poses);
+  std::vector<uint8_t> staged((size_t)n_scans, 0);
+  for (int32_t k = 0; k < n_poses; ++k) {
+    const int32_t i = scan_index ? scan_index[k] : k;
+    const int32_t n = (int32_t)(point_offsets[i + 1] - point_offsets[i]);
+    const int32_t step = csm::map_check_step(n, p->check_point_num), nc = csm::map_check_checked(n, step);
+    csm::map_check_pose(m->scale_factor, m->off_x, m->off_y, m->size_x, m->size_y, poses + 3 * (size_t)k, &rec[k]);
+    rec[k].pt_begin = at[(size_t)i];
+    rec[k].step = 1;  // the staging holds the checked points alone
+    rec[k].n_checked = nc;
+    if (staged[(size_t)i]) continue;
+    staged[(size_t)i] = 1;
+    const double* src = points_m + 2 * point_offsets[i];
+    double* dst = up + 2 * at[(size_t)i];
+    for (int32_t c = 0; c < nc; ++c) {
+      dst[2 * c] = src[2 * ((int64_t)c * step)];
+      dst[2 * c + 1] = src[2 * ((int64_t)c * step) + 1];
+    }
+  }
+  if ((st = check_run(m, n_poses, (size_t)n_up * 16, nullptr, *p)) != CSM_OK) return st;
+  check_finish(m, n_poses, *p, coeff, counts);
+  return CSM_OK;
+}
+
+int csm_gridmap_feedback_penalty_store(csm_gridmap* m, csm_scan_store* store, int32_t n_poses, const int32_t* scan_ids,
+                                       const double* poses, const csm_map_check_param* p, double* coeff,
+                                       int32_t* counts) {
+  if (!m || !store || !p || n_poses < 0 || (n_poses > 0 && (!scan_ids || !poses || !coeff)))
+    return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (n_poses == 0) return CSM_OK;
+  if (csm::map_check_guard(p->check_point_num, p->bound_tolerance, p->penalty_gain)) {
+    check_guarded(n_poses, *p, coeff, counts);
+    return CSM_OK;
+  }
+  DeviceGuard g(m->device);
+  // held until the stream is drained: no reader of the store's buffer outlives the call
+  csm::ScanStoreView v;
+  const std::unique_lock<std::mutex> slk = csm::scan_store_lock(store, &v);
+  int st;
+  if ((st = check_store_records(m, v, n_poses, scan_ids, poses, *p)) != CSM_OK) return st;
+  if ((st = check_run(m, n_poses, 0, v.pts, *p)) != CSM_OK) return st;
+  check_finish(m, n_poses, *p, coeff, counts);
+  return CSM_OK;
+}
+
+int csm_gridmap_map_check_launches(csm_gridmap* m, int64_t* launches) {
+  if (!m || !launches) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  *launches = m->check_launches;
+  return CSM_OK;
+}
+
+int csm_gridmap_feedback_penalty_store_kernel_ms(csm_gridmap* m, csm_scan_store* store, int32_t n_poses,
+                                                 const int32_t* scan_ids, const double* poses,
+                                                 const csm_map_check_param* p, int32_t repeats, double* ms) {
+  if (!m || !store || !p || n_poses <= 0 || !scan_ids || !poses || repeats <= 0 || !ms) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (csm::map_check_guard(p->check_point_num, p->bound_tolerance, p->penalty_gain))
+    return m->fail(CSM_ERR_INVALID_ARG, "map check: the guard answers these arguments, no kernel runs");
+  DeviceGuard g(m->device);
+  csm::ScanStoreView v;
+  const std::unique_lock<std::mutex> slk = csm::scan_store_lock(store, &v);
+  int st;
+  if ((st = check_store_records(m, v, n_poses, scan_ids, poses, *p)) != CSM_OK) return st;
+  if ((st = check_upload(m, n_poses, 0)) != CSM_OK) return st;
+  csmh::Event e0, e1;
+  GM_HIP(e0.create(hipEventDefault));
+  GM_HIP(e1.create(hipEventDefault));
+  GM_HIP(hipEventRecord(e0, m->stream));
+  for (int r = 0; r < repeats; ++r) GM_HIP(check_launch(m, n_poses, v.pts, *p));
+  GM_HIP(hipEventRecord(e1, m->stream));
+  GM_HIP(hipStreamSynchronize(m->stream));
+  float total = 0.f;
+  GM_HIP(hipEventElapsedTime(&total, e0, e1));
+  *ms = (double)total / repeats;
   return CSM_OK;
 }
 

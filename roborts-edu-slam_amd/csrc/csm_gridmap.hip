@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "csm_gridmap_internal.hpp"
+#include "csm_map_check_plan.hpp"
 
 #pragma clang fp contract(off)
 
@@ -260,6 +261,83 @@ __global__ __launch_bounds__(kThreads) void feedback_kernel(const GmEnd* __restr
   if (__builtin_amdgcn_ballot_w64(hit) != 0 && lane == 0) atomicAdd(count, 1);
 }
 
+// (int)(v + 0.5) where the host's cast is defined. A NaN, an infinity or a
+// value past the range is INT_MIN on the host (x86 cvttsd2si), which fails
+// PointInMap: such a point is skipped (cell_of in csm_chain_maps.hip).
+__device__ __forceinline__ bool check_cell_of(double v, int* out) {
+  const double r = v + 0.5;
+  if (!(r > -2147483648.0 && r < 2147483647.0)) return false;
+  *out = (int)r;
+  return true;
+}
+
+// The cell test of CheckOccuLineVisitorCallback (:447-471) as feedback_kernel
+// makes it: the blur offset, CountCell's or ProbabilityCell's GetGridStates.
+__device__ __forceinline__ bool check_occupied(const GmCells& C, const GmOps& P, int use_blur, double occu_offset,
+                                               int64_t c) {
+  if (use_blur) return (double)C.prob[c] > occu_offset;
+  if (P.kind == kGmCount)  // CountCellFunctions::GetGridStates :125-136
+    return C.pass[c] >= P.min_pass && !(C.prob[c] < P.occu_threshold);
+  return C.prob[c] > 0.5f;  // ProbabilityCellFunctions::GetGridStates :367-375
+}
+
+// MapFeedbackResponsePenalty for many poses on one map: a workgroup per pose
+// record (csm_map_check_plan.hpp), its waves take the pose's checked points in
+// turn, lanes over a ray's line cells as in feedback_kernel. A point is
+// scaled and transformed here exactly as the host does it: raw * factor
+// (CreateFrom, sensor_data_manager.h:99-115: one rounding), then pose_apply's
+// expression (contraction is off in this file), then (int)(v + 0.5). A ray's
+// result saturates at 1, so a wave leaves the ray at its first ballot with a
+// hit. Every branch below is uniform over the wave. The waves' counts meet in
+// LDS and one lane stores counts[pose]: no clear, no atomics.
+__global__ __launch_bounds__(kThreads) void feedback_batch_kernel(const MapCheckPose* __restrict__ poses,
+                                                                   const double* __restrict__ pts, double factor,
+                                                                   GmCells C, GmOps P, int use_blur,
+                                                                   double occu_offset, int64_t min_d2,
+                                                                   int* __restrict__ counts) {
+  constexpr int kWaves = kThreads / 64;
+  __shared__ int wave_hits[kWaves];
+  const MapCheckPose R = poses[blockIdx.x];
+  // the wave's index as a scalar: the point's address, the transform and the line are then the wave's, not a lane's
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x / 64)), lane = threadIdx.x & 63;
+  int hits = 0;
+  for (int k = wave; !R.no_rays && k < R.n_checked; k += kWaves) {
+    const double* q = pts + 2 * (R.pt_begin + (int64_t)k * R.step);
+    const double px = q[0] * factor, py = q[1] * factor;
+    const double ex = (R.c * px + (-R.s) * py) + R.tx;
+    const double ey = (R.s * px + R.c * py) + R.ty;
+    int x1, y1;
+    if (!check_cell_of(ex, &x1) || !check_cell_of(ey, &y1)) continue;
+    if ((x1 == R.x0 && y1 == R.y0) || !in_map(C, x1, y1, 0)) continue;  // :379
+    const Line L(R.x0, R.y0, x1, y1);
+    for (int t0 = 0; t0 <= L.dx; t0 += 64) {
+      const int t = t0 + lane;
+      bool hit = false;
+      if (t <= L.dx) {
+        int x, y;
+        L.at(t, x, y);
+        // a cell outside the grid is not occupied
+        if (x >= 0 && y >= 0 && x < C.size_x && y < C.size_y &&
+            check_occupied(C, P, use_blur, occu_offset, (int64_t)y * C.row + x)) {
+          const int64_t dx = (int64_t)x1 - x, dy = (int64_t)y1 - y;
+          hit = dx * dx + dy * dy >= min_d2;
+        }
+      }
+      if (__builtin_amdgcn_ballot_w64(hit) != 0) {
+        ++hits;
+        break;
+      }
+    }
+  }
+  if (lane == 0) wave_hits[wave] = hits;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int sum = 0;
+    for (int w = 0; w < kWaves; ++w) sum += wave_hits[w];
+    counts[blockIdx.x] = sum;
+  }
+}
+
 // `new CellType[n]{default_cell_prob_}` (grid_map_base.h:160,214): element 0
 // from default_cell_prob_, the others default-constructed (kDefaultCellProb).
 __global__ __launch_bounds__(kThreads) void fresh_kernel(GmCells C, int64_t n, float first) {
@@ -412,6 +490,14 @@ hipError_t gm_launch_feedback(const GmEnd* ends, int n, int sx, int sy, const Gm
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(feedback_kernel, dim3((unsigned)((n + 3) / 4)), dim3(kThreads), 0, s, ends, n, sx, sy, C, P,
                      use_blur, (float)occu_offset, occu_offset, min_d2, count);
+  return hipGetLastError();
+}
+hipError_t gm_launch_feedback_batch(const MapCheckPose* poses, int n_poses, const double* pts, double factor,
+                                    const GmCells& C, const GmOps& P, int use_blur, double occu_offset,
+                                    int64_t min_d2, int* counts, hipStream_t s) {
+  if (n_poses <= 0) return hipSuccess;
+  hipLaunchKernelGGL(feedback_batch_kernel, dim3((unsigned)n_poses), dim3(kThreads), 0, s, poses, pts, factor, C, P,
+                     use_blur, occu_offset, min_d2, counts);
   return hipGetLastError();
 }
 hipError_t gm_launch_states(const GmCells& C, const GmOps& P, int x0, int y0, int w, int h, int8_t* out,

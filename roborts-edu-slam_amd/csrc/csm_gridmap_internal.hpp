@@ -55,6 +55,13 @@ hipError_t gm_launch_lines(const GmEnd* ends, int n, int sx, int sy, const GmCel
                            uint64_t* fkey, uint32_t* oseq, uint32_t seq, int tol, hipStream_t s);
 hipError_t gm_launch_feedback(const GmEnd* ends, int n, int sx, int sy, const GmCells& C, const GmOps& P,
                               int use_blur, double occu_offset, int64_t min_d2, int* count, hipStream_t s);
+// The map check of n_poses pose records (csm_map_check_plan.hpp) in one
+// launch: pts the points the records index (metres, x then y), factor =
+// 1 / resolution, counts[k] the rays of pose k that hit.
+struct MapCheckPose;
+hipError_t gm_launch_feedback_batch(const MapCheckPose* poses, int n_poses, const double* pts, double factor,
+                                    const GmCells& C, const GmOps& P, int use_blur, double occu_offset,
+                                    int64_t min_d2, int* counts, hipStream_t s);
 // GetGridStates (100 / 0 / -1) of the box (x0, y0, w, h), row-major into
 // out[h * w] (device, 4-byte aligned; w * h below 2^31). Cells are read at the
 // linear index y * size_x + x; -1 for a negative x or y or an index past the array.

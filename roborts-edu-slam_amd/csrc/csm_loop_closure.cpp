@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "csm_exchange.hpp"
+#include "csm_gridmap_internal.hpp"
 
 namespace {
 
@@ -740,6 +741,31 @@ int csm_loop_closure_match_gated_full(csm_loop_closure* lc, const double* pts, i
   lc->workers->run(run);
   for (int r = 0; r < G; ++r)
     if (status[(size_t)r] != CSM_OK) return lc->fail(status[(size_t)r], errs[(size_t)r]);
+  return CSM_OK;
+}
+
+int csm_loop_closure_map_check(csm_loop_closure* lc, csm_gridmap* pub_map, int32_t scan_id,
+                               const csm_map_check_param* param, const csm_loop_closure_result* results, int32_t n,
+                               double* penalties) {
+  if (!lc || !pub_map || !param || n < 0 || (n > 0 && (!results || !penalties))) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(lc->mu);
+  csm::GridMapView view;
+  int st = csm::gridmap_view(pub_map, &view);
+  if (st != CSM_OK) return lc->fail(st, "map check: the pub map gave no view");
+  size_t r = 0;
+  while (r < lc->devices.size() && lc->devices[r] != view.device) ++r;
+  if (r == lc->devices.size())
+    return lc->fail(CSM_ERR_INVALID_ARG, "map check: the pub map lives on device " + std::to_string(view.device) +
+                                             ", which is none of the loop closure's");
+  if (n == 0) return CSM_OK;
+  if (lc->stores.empty()) return lc->fail(CSM_ERR_INVALID_ARG, "map check: no kept scan of that id");
+  std::vector<int32_t> ids((size_t)n, scan_id);
+  std::vector<double> poses((size_t)n * 3);
+  for (int32_t k = 0; k < n; ++k) std::memcpy(&poses[(size_t)3 * k], results[k].pose_world, 3 * sizeof(double));
+  DeviceRestore restore;
+  st = csm_gridmap_feedback_penalty_store(pub_map, lc->stores[r], n, ids.data(), poses.data(), param, penalties,
+                                          nullptr);
+  if (st != CSM_OK) return lc->fail(st, std::string("map check: ") + csm_gridmap_last_error(pub_map));
   return CSM_OK;
 }
 

@@ -56,6 +56,10 @@ EXPORTED = (
     "csm_loop_closure_set_submaps", "csm_loop_closure_match", "csm_loop_closure_match_full",
     "csm_loop_closure_match_gated", "csm_loop_closure_match_gated_full",
     "csm_loop_closure_add_scan", "csm_loop_closure_set_scan_pose", "csm_loop_closure_set_submaps_chains",
+    "csm_loop_closure_map_check",
+    # include/csm_map_check.h
+    "csm_gridmap_feedback_penalty_batch", "csm_gridmap_feedback_penalty_store", "csm_gridmap_map_check_launches",
+    "csm_gridmap_feedback_penalty_store_kernel_ms",
     # include/csm_chain_maps.h
     "csm_scan_store_create", "csm_scan_store_destroy", "csm_scan_store_last_error", "csm_scan_store_add",
     "csm_scan_store_set_pose", "csm_scan_store_count", "csm_set_grid_stack_chains", "csm_grid_download",
@@ -249,6 +253,18 @@ class CsmChainMapParam(C.Structure):
         ("reserved", C.c_int32),
         ("default_cell_prob", C.c_float),
         ("reserved_f", C.c_float),
+    ]
+
+
+class CsmMapCheckParam(C.Structure):
+    """csm_map_check_param (include/csm_map_check.h)."""
+    _fields_ = [
+        ("check_point_num", C.c_int32),
+        ("use_blur", C.c_int32),
+        ("use_logistic", C.c_int32),
+        ("reserved", C.c_int32),
+        ("bound_tolerance", C.c_double),
+        ("penalty_gain", C.c_double),
     ]
 
 
@@ -455,6 +471,15 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         "csm_loop_closure_set_scan_pose": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
         "csm_loop_closure_set_submaps_chains": (C.c_int, [C.c_void_p, C.POINTER(CsmChainMapParam), C.c_int32, _i32p,
                                                           _i32p, _dp]),
+        "csm_loop_closure_map_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CsmMapCheckParam),
+                                                 C.POINTER(CsmLoopClosureResult), C.c_int32, _dp]),
+        "csm_gridmap_feedback_penalty_batch": (C.c_int, [C.c_void_p, C.c_int32, _dp, _i64p, C.c_int32, _i32p, _dp,
+                                                         C.POINTER(CsmMapCheckParam), _dp, _i32p]),
+        "csm_gridmap_feedback_penalty_store": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _i32p, _dp,
+                                                         C.POINTER(CsmMapCheckParam), _dp, _i32p]),
+        "csm_gridmap_map_check_launches": (C.c_int, [C.c_void_p, _i64p]),
+        "csm_gridmap_feedback_penalty_store_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _i32p, _dp,
+                                                                   C.POINTER(CsmMapCheckParam), C.c_int32, _dp]),
         "csm_scan_store_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
         "csm_scan_store_destroy": (C.c_int, [C.c_void_p]),
         "csm_scan_store_last_error": (C.c_char_p, [C.c_void_p]),

@@ -8,6 +8,8 @@ reads and checks against:
   UpdateMapByRange                         ~ map/occu_grid_map.h:258-329
   InitMapWithRangeVec                      ~ map/occu_grid_map.h:222-255
   MapFeedbackResponsePenalty               ~ map/occu_grid_map.h:331-392
+  feedback_penalty_batch / _store          ~ SlamProcessor::MapCheckPenalize (slam_processor.cpp:573-595)
+                                             for many poses in one launch (include/csm_map_check.h)
   GetGridStates / OccupancyGrid            ~ SlamNode::PublishMapThread's cell loop, box and
                                              origin (roborts_slam_node.cpp:355-488)
 
@@ -22,7 +24,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from ._abi import COUNT_CELL, PROBABILITY_CELL, CsmGridmapState, CsmOccupancyGridInfo
+from ._abi import COUNT_CELL, PROBABILITY_CELL, CsmGridmapState, CsmMapCheckParam, CsmOccupancyGridInfo
 
 _lib = _abi.load_library()
 
@@ -134,6 +136,74 @@ class OccuGridMap:
                                                       int(check_point_num), float(bound_tolerance),
                                                       float(penalty_gain), int(use_blur), C.byref(out)))
         return out.value
+
+    # -- the batched map check (include/csm_map_check.h) ---------------------------
+    @staticmethod
+    def _check_param(check_point_num, bound_tolerance, penalty_gain, use_blur, use_logistic) -> CsmMapCheckParam:
+        return CsmMapCheckParam(int(check_point_num), int(bool(use_blur)), int(bool(use_logistic)), 0,
+                                float(bound_tolerance), float(penalty_gain))
+
+    def feedback_penalty_batch(self, scans_m, poses, check_point_num: int, bound_tolerance: float,
+                               penalty_gain: float, use_blur: bool = False, use_logistic: bool = False,
+                               scan_index=None):
+        """csm_gridmap_feedback_penalty_batch: MapCheckPenalize of pose k on
+        scan scan_index[k] (None: scan k) in one launch -> (penalties float64
+        [n_poses], counts int32 [n_poses]: the rays that hit, -1 for a pose
+        outside the map). scans_m: sensor-frame end points in METRES (the
+        map's 1/resolution is applied on the device)."""
+        scans = [_d(s, (-1, 2)) for s in scans_m]
+        pts = np.ascontiguousarray(np.concatenate(scans)) if scans else np.zeros((0, 2))
+        off = np.zeros(len(scans) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([s.shape[0] for s in scans])
+        w = _d(poses, (-1, 3))
+        idx = None if scan_index is None else np.ascontiguousarray(scan_index, dtype=np.int32).reshape(-1)
+        if idx is not None and idx.size != w.shape[0]:
+            raise ValueError("scan_index: one scan per pose")
+        prm = self._check_param(check_point_num, bound_tolerance, penalty_gain, use_blur, use_logistic)
+        coeff = np.empty(w.shape[0], dtype=np.float64)
+        counts = np.empty(w.shape[0], dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._check(_lib.csm_gridmap_feedback_penalty_batch(
+            self._h, len(scans), _dp(pts), off.ctypes.data_as(C.POINTER(C.c_int64)), w.shape[0],
+            None if idx is None else idx.ctypes.data_as(i32p), _dp(w), C.byref(prm), _dp(coeff),
+            counts.ctypes.data_as(i32p)))
+        return coeff, counts
+
+    def feedback_penalty_store(self, store, scan_ids, poses, check_point_num: int, bound_tolerance: float,
+                               penalty_gain: float, use_blur: bool = False, use_logistic: bool = False):
+        """csm_gridmap_feedback_penalty_store: the same with the scans read in
+        place from a chain_maps.ScanStore on this map's device -> (penalties,
+        counts)."""
+        ids = np.ascontiguousarray(scan_ids, dtype=np.int32).reshape(-1)
+        w = _d(poses, (-1, 3))
+        if ids.size != w.shape[0]:
+            raise ValueError("scan_ids: one kept scan per pose")
+        prm = self._check_param(check_point_num, bound_tolerance, penalty_gain, use_blur, use_logistic)
+        coeff = np.empty(ids.size, dtype=np.float64)
+        counts = np.empty(ids.size, dtype=np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._check(_lib.csm_gridmap_feedback_penalty_store(self._h, store._h, ids.size, ids.ctypes.data_as(i32p),
+                                                            _dp(w), C.byref(prm), _dp(coeff),
+                                                            counts.ctypes.data_as(i32p)))
+        return coeff, counts
+
+    def map_check_launches(self) -> int:
+        """csm_gridmap_map_check_launches: the batch kernel's launches on this map so far."""
+        n = C.c_int64(0)
+        self._check(_lib.csm_gridmap_map_check_launches(self._h, C.byref(n)))
+        return int(n.value)
+
+    def feedback_penalty_store_kernel_ms(self, store, scan_ids, poses, check_point_num: int, bound_tolerance: float,
+                                         penalty_gain: float, use_blur: bool = False, repeats: int = 20) -> float:
+        """csm_gridmap_feedback_penalty_store_kernel_ms: the batch kernel of that call alone, by HIP events."""
+        ids = np.ascontiguousarray(scan_ids, dtype=np.int32).reshape(-1)
+        w = _d(poses, (-1, 3))
+        prm = self._check_param(check_point_num, bound_tolerance, penalty_gain, use_blur, False)
+        ms = C.c_double(0.0)
+        self._check(_lib.csm_gridmap_feedback_penalty_store_kernel_ms(
+            self._h, store._h, ids.size, ids.ctypes.data_as(C.POINTER(C.c_int32)), _dp(w), C.byref(prm),
+            int(repeats), C.byref(ms)))
+        return ms.value
 
     # -- getters ---------------------------------------------------------------------
     def state(self) -> CsmGridmapState:

@@ -285,6 +285,27 @@ class DeviceLoopClosure:
         coordinates."""
         return self._gated(points_cells, param, pose_world, min_response, capacity, covs)
 
+    def map_check(self, pub_map, scan_id: int, poses_world, check_point_num: int, bound_tolerance: float,
+                  penalty_gain: float, use_blur: bool = False, use_logistic: bool = True) -> np.ndarray:
+        """csm_loop_closure_map_check: MapCheckPenalize of the kept scan
+        `scan_id` at each of poses_world (e.g. last_pose_worlds of a gated
+        match) on pub_map (gridmap.OccuGridMap on one of this handle's
+        devices), one launch -> penalties float64 [n]. The caller multiplies
+        its response and clamps to 1 (slam_processor.cpp:318-319)."""
+        from ._abi import CsmLoopClosureResult, CsmMapCheckParam
+        C = self._C
+        w = np.ascontiguousarray(poses_world, dtype=np.float64).reshape(-1, 3)
+        n = w.shape[0]
+        res = (CsmLoopClosureResult * max(n, 1))()
+        for k in range(n):
+            res[k].pose_world[:] = w[k].tolist()
+        prm = CsmMapCheckParam(int(check_point_num), int(bool(use_blur)), int(bool(use_logistic)), 0,
+                               float(bound_tolerance), float(penalty_gain))
+        out = np.empty(n, dtype=np.float64)
+        self._check(self._lib.csm_loop_closure_map_check(self._h, pub_map.handle, int(scan_id), C.byref(prm), res, n,
+                                                         out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.csm_loop_closure_destroy(self._h)
