@@ -151,12 +151,99 @@ int csm_loop_closure_match_gated_full(csm_loop_closure* lc, const double* points
  * penalties[k] = that penalty of the kept scan scan_id at results[k].pose_world, k < n,
  * on pub_map: csm_gridmap_feedback_penalty_store (csm_map_check.h) over this handle's
  * store on pub_map's device, one launch for all n. Only penalties is written: the
- * loop-closure window is one wide level, not the reference's three, so the score it
- * would multiply is the caller's to choose. CSM_ERR_INVALID_ARG when none of the
- * handle's devices is the map's, or scan_id is no kept scan. */
+ * score the reference multiplies it with is the mean of three levels, which
+ * csm_loop_closure_scan_match (below) computes, penalty and clamp included.
+ * CSM_ERR_INVALID_ARG when none of the handle's devices is the map's, or scan_id is
+ * no kept scan. */
 int csm_loop_closure_map_check(csm_loop_closure* lc, csm_gridmap* pub_map, int32_t scan_id,
                                const csm_map_check_param* param, const csm_loop_closure_result* results,
                                int32_t n, double* penalties);
+
+/* SlamProcessor::ScanMatchInterface (slam/slam_processor.cpp:250-326) for every
+ * gated submap: the number TryCloseLoop and LinkNearChains compare with their
+ * thresholds (pose_graph/range_scan_pose_graph.cpp:153,312,329), with the pose
+ * and covariance the call leaves. The Gauss-Newton matcher is off, as both
+ * reference YAMLs have it (with it on, csm_backend.h remains). */
+typedef struct csm_loop_closure_interface_param {
+  csm_param levels[3];          /* the ScanMatchParam set of the call; levels[0] is the (wide) coarse window   */
+  int32_t use_fine_scan_match;  /* ScanMatchInterface's argument (scan_matchers.h:247)                          */
+  int32_t use_map_check;        /* 0: penalty 1, pub_map may be NULL                                            */
+  double range_max;             /* the range finder's, for MapSizeCheck (scan_matchers.h:365-390)               */
+  double min_response;          /* gate on level 0's unclamped best, inclusive, as csm_loop_closure_match_gated */
+  csm_map_check_param check;    /* use_logistic = 1 is what ScanMatchInterface passes (:315)                    */
+} csm_loop_closure_interface_param;
+
+typedef struct csm_loop_closure_interface_result {
+  int32_t submap, levels_run;   /* 1 or 3 */
+  double pose[3];               /* best_pose out (world)                        */
+  double cov[9];                /* cov_matrix out, row-major                    */
+  double score;                 /* ScanMatchInterface's return value            */
+  double response[3];           /* each level's clamped response (not run: 0)   */
+  double map_penalty;
+  csm_loop_closure_result wide; /* what csm_loop_closure_match_gated_full writes for this submap */
+  csm_match_result wide_match;
+} csm_loop_closure_interface_result;
+
+/* The query is the kept scan scan_id (csm_loop_closure_add_scan; the handle
+ * keeps its raw points on the host too): its matcher points are raw * (1 /
+ * resolution) with the submaps' resolution, rounded once, as CreateFrom does
+ * (sensor_data_manager.h:99-115). The submaps come from
+ * csm_loop_closure_set_submaps_chains, or from csm_loop_closure_set_submaps
+ * with every submap's offset equal to info->offset_x / offset_y (the fine
+ * levels convert poses with the stack's one geometry; otherwise
+ * CSM_ERR_UNSUPPORTED when use_fine_scan_match is set).
+ *
+ * For every submap whose level-0 best is >= param->min_response, results[k] is
+ * what ScanMatchInterface(range_data(scan_id), ., chain k, best_pose =
+ * pose_world, cov = cov_init (NULL: identity), use_fine_scan_match, .) returns
+ * and writes, k < min(*n_pass, capacity), in ascending submap order; *n_pass
+ * counts every passing submap. The steps:
+ *   1. level 0 as csm_loop_closure_match_gated_full: the same shards, finish and
+ *      paths, cov_init going in for every entry;
+ *   2. the next level's start pose: the averaged pose's world coordinates when
+ *      wide_match.accepted, else pose_world unchanged
+ *      (correlate_scan_matcher.h:866-869);
+ *   3. with use_fine_scan_match, levels 1 and 2 (scan_matchers.h:247-261): each
+ *      device runs all its passers in one seeded batch over its resident stack
+ *      (the driver behind csm_scan_matchers_batch_grids_seeded, first_level = 1,
+ *      the clamped level-0 responses as the seed, poses and covariances as level
+ *      0 left them), the devices concurrently;
+ *   4. with use_map_check, MapCheckPenalize of the kept scan at every entry's
+ *      final pose on pub_map: one csm_gridmap_feedback_penalty_store, the path
+ *      of csm_loop_closure_map_check;
+ *   5. score = min(mean * penalty, 1.0), the mean over the levels run
+ *      (scan_matchers.h:281, slam_processor.cpp:316-317).
+ * The strict > / < comparisons of the pose graph stay with the caller. A final
+ * score above T needs a level-0 best above 3 T - 2 with three levels (every
+ * response is clamped to 1 and the logistic penalty never exceeds 1), above T
+ * with one: min_response = 3 T - 2 loses nothing (csrc/csm_lc_interface.hpp
+ * interface_wide_gate; not with check.use_logistic = 0, whose penalty reaches
+ * 1 + 2 * penalty_gain).
+ *
+ * MapSizeCheck cannot grow a submap here: the reference's box, pose_world in
+ * map cells +- (range_max + levels[0].search_space_size) / cell length, is
+ * tested against every submap with UpdateBound's criterion
+ * (grid_map_base.h:247-264) before anything is launched; where the reference
+ * would grow its map the call returns CSM_ERR_UNSUPPORTED and
+ * csm_loop_closure_last_error names the submap size that would have fit.
+ * CSM_ERR_INVALID_ARG: levels[*].type == CSM_FAST, a NaN gate, capacity < 0,
+ * scan_id of no kept scan, use_map_check without a map on one of the handle's
+ * devices. A failed call leaves the handle usable and its submaps resident. */
+int csm_loop_closure_scan_match(csm_loop_closure* lc, csm_gridmap* pub_map, int32_t scan_id,
+                                const csm_loop_closure_interface_param* param, const double pose_world[3],
+                                const double cov_init[9] /* NULL: identity */,
+                                csm_loop_closure_interface_result* results, int32_t capacity, int32_t* n_pass);
+
+/* The largest min_response that loses no submap whose final score exceeds `threshold` (the caller's
+ * strict >), for levels_run = 3 (3 * threshold - 2, lowered by the roundings in between) or 1
+ * (threshold itself); csrc/csm_lc_interface.hpp interface_wide_gate. Holds for a penalty <= 1: the
+ * logistic map check or none, not check.use_logistic = 0. Host only. */
+double csm_loop_closure_wide_gate(double threshold, int32_t levels_run);
+
+/* Borrow the matcher context of the handle's device `shard` (0 .. n_devices - 1),
+ * e.g. for csm_set_profiling / csm_kernel_stats around a call (as
+ * csm_backend_matcher). The handle keeps owning it. */
+int csm_loop_closure_matcher(csm_loop_closure* lc, int32_t shard, csm_ctx** ctx);
 
 #ifdef __cplusplus
 }

@@ -31,7 +31,8 @@ struct BorrowedBatch {
 // scan_matchers.h:205-281): the levels from first_level on, each scan's running
 // sum started from score_seed and the seed counted as one term of the mean.
 int csmh::matchers_loaded_locked(csm_ctx* c, const csm_param all_levels[3], int32_t use_fine, double* poses,
-                                 double* covs, double* scores, int32_t first_level, const double* score_seed) {
+                                 double* covs, double* scores, int32_t first_level, const double* score_seed,
+                                 double* level_resp) {
   if (c->n_scans < 0) return c->fail(CSM_ERR_INVALID_ARG, "no scans loaded (csm_load_scans)");
   if (!c->has_grid) return c->fail(CSM_ERR_NO_GRID, "no grid set");
   const int32_t n_scans = c->n_scans;
@@ -55,7 +56,7 @@ int csmh::matchers_loaded_locked(csm_ctx* c, const csm_param all_levels[3], int3
   if (fast && grid) return c->fail(CSM_ERR_UNSUPPORTED, "FAST windows read grid 0 only");
   if (n_scans >= c->pipeline_min && !fast) {
     if ((st = match_levels_pipelined(c, n_scans, c->scan_off.data(), levels, n_levels, poses, covs,
-                                     sum.data(), grid)) != CSM_OK)
+                                     sum.data(), grid, level_resp)) != CSM_OK)
       return st;
   } else {
     for (int l = 0; l < n_levels; ++l) {
@@ -63,6 +64,7 @@ int csmh::matchers_loaded_locked(csm_ctx* c, const csm_param all_levels[3], int3
                             grid, c->skip_dead_lists ? live_lists(levels, n_levels, l) : 0)) != CSM_OK)
         return st;
       for (int s = 0; s < n_scans; ++s) sum[(size_t)s] += resp[(size_t)s];
+      if (level_resp) std::copy(resp.begin(), resp.end(), level_resp + (size_t)l * n_scans);
     }
   }
   for (int s = 0; s < n_scans; ++s) scores[s] = sum[(size_t)s] / times;  // :281
@@ -71,6 +73,21 @@ int csmh::matchers_loaded_locked(csm_ctx* c, const csm_param all_levels[3], int3
     c->account("host:call", (float)(c->t_exit - t_call), 0.0, 0.0);
   }
   return CSM_OK;
+}
+
+int csmh::scan_matchers_batch_grids_levels(csm_ctx* c, int32_t n_scans, const double* pts, const int64_t* offsets,
+                                           const int32_t* grid_index, const csm_param levels[3], int32_t first_level,
+                                           int32_t use_fine, const double* score_seed, double* poses, double* covs,
+                                           double* scores, double* level_resp) {
+  if (!c || !levels || !poses || !covs || !scores) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  DeviceGuard g(c->device);
+  if (first_level < 0 || first_level > 1 || (first_level == 1 && !use_fine))
+    return c->fail(CSM_ERR_INVALID_ARG, "first_level must be 0, or 1 with use_fine");
+  int st = load_scans_locked(c, n_scans, pts, offsets);
+  if (st != CSM_OK) return st;
+  if (grid_index) c->scan_grid.assign(grid_index, grid_index + n_scans);
+  return matchers_loaded_locked(c, levels, use_fine, poses, covs, scores, first_level, score_seed, level_resp);
 }
 
 extern "C" {
@@ -229,15 +246,8 @@ int csm_scan_matchers_batch_grids_seeded(csm_ctx* c, int32_t n_scans, const doub
                                          const int32_t* grid_index, const csm_param levels[3], int32_t first_level,
                                          int32_t use_fine, const double* score_seed, double* poses, double* covs,
                                          double* scores) {
-  if (!c || !levels || !poses || !covs || !scores) return CSM_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(c->mu);
-  DeviceGuard g(c->device);
-  if (first_level < 0 || first_level > 1 || (first_level == 1 && !use_fine))
-    return c->fail(CSM_ERR_INVALID_ARG, "first_level must be 0, or 1 with use_fine");
-  int st = load_scans_locked(c, n_scans, pts, offsets);
-  if (st != CSM_OK) return st;
-  if (grid_index) c->scan_grid.assign(grid_index, grid_index + n_scans);
-  return matchers_loaded_locked(c, levels, use_fine, poses, covs, scores, first_level, score_seed);
+  return scan_matchers_batch_grids_levels(c, n_scans, pts, offsets, grid_index, levels, first_level, use_fine,
+                                          score_seed, poses, covs, scores, nullptr);
 }
 
 }  // extern "C"

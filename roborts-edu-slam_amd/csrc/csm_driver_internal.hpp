@@ -110,6 +110,7 @@ struct PipeJob {
   double *poses = nullptr, *covs = nullptr, *sum = nullptr;
   double* scores = nullptr;  // submitted: scores[s] = sum[s] / n_levels when complete
   std::vector<double> resp, own_sum;
+  double* level_resp = nullptr;  // nullable: level l's responses to level_resp[l * n_scans + s] (matchers_loaded_locked)
   int32_t first[csm_ctx::kMaxParts]{}, count[csm_ctx::kMaxParts]{};
   // by level parity: level l's run and level l + 1's, per part. Reused across
   // batches: a fresh run's window plans (64 B each, 128 KB per 2048 windows)
@@ -177,6 +178,6 @@ int pipe_abort(csm_ctx* c, int st);
 int pipe_last_launches(csm_ctx* c);
 int match_levels_pipelined(csm_ctx* c, int32_t n_scans, const int64_t* offsets, const csm_param* levels,
                            int n_levels, double* poses, double* covs, double* sum,
-                           const int32_t* scan_grid = nullptr);
+                           const int32_t* scan_grid = nullptr, double* level_resp = nullptr);
 
 }  // namespace csmh

@@ -42,6 +42,7 @@
 #include "csm_level_decision.hpp"
 #include "csm_grid_copies.hpp"
 
+#include "csm_driver_levels.hpp"
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -920,7 +921,10 @@ int ranges_ingest(csm_ctx* c, csm_ctx::Staged& S, const csm_laser& L, double thr
 int repair_deskewed(csm_ctx* c, csm_ctx::Staged& S);
 // csm_driver.cpp
 // first_level / score_seed: csm_scan_matchers_batch_grids_seeded (0 and null: the plain forms)
+// level_resp (nullable): each level's responses, level first_level + l's to level_resp[l * n_scans + s]
 int matchers_loaded_locked(csm_ctx* c, const csm_param levels[3], int32_t use_fine, double* poses, double* covs,
-                           double* scores, int32_t first_level = 0, const double* score_seed = nullptr);
+                           double* scores, int32_t first_level = 0, const double* score_seed = nullptr,
+                           double* level_resp = nullptr);
+// (scan_matchers_batch_grids_levels, the entry over it: csm_driver_levels.hpp)
 
 }  // namespace csmh

@@ -25,6 +25,8 @@
 
 #include "csm_exchange.hpp"
 #include "csm_gridmap_internal.hpp"
+#include "csm_driver_levels.hpp"
+#include "csm_lc_interface.hpp"
 
 namespace {
 
@@ -164,6 +166,7 @@ struct csm_loop_closure {
   std::vector<int> devices;
   std::vector<csm_ctx*> ctx;
   std::vector<csm_scan_store*> stores;  // the kept scans, replicated: one store per device (made by the first add_scan)
+  std::vector<std::vector<double>> scan_pts;  // ... and their raw points (m) on the host: csm_loop_closure_scan_match's query
   std::vector<ncclComm_t> comms;
   std::vector<hipStream_t> streams;
   std::vector<csm::LcExchange*> xbuf;  // device, one per device
@@ -174,6 +177,10 @@ struct csm_loop_closure {
   bool broken = false;
   double resolution = 0.0;
   std::vector<double> offsets;
+  // the submaps' common size, and the one map offset their stacks' geometry carries (what the
+  // level drivers convert poses with)
+  int32_t size_x = 0, size_y = 0;
+  double stack_offset[2] = {0.0, 0.0};
   std::vector<int32_t> lo, hi;
   std::unique_ptr<ShardWorkers> workers;
 
@@ -289,6 +296,10 @@ int csm_loop_closure_set_submaps(csm_loop_closure* lc, const float* cells, int32
   lc->hi.swap(hi);
   lc->resolution = info->resolution;
   lc->offsets.assign(offsets, offsets + 2 * (size_t)n_submaps);
+  lc->size_x = info->size_x;
+  lc->size_y = info->size_y;
+  lc->stack_offset[0] = info->offset_x;
+  lc->stack_offset[1] = info->offset_y;
   lc->n_submaps = n_submaps;
   return CSM_OK;
 }
@@ -328,6 +339,8 @@ int csm_loop_closure_add_scan(csm_loop_closure* lc, const double* points_m, int3
       return lc->fail(CSM_ERR_HIP, "the devices' scan stores are out of step");
     }
   }
+  if (lc->scan_pts.size() <= (size_t)first) lc->scan_pts.resize((size_t)first + 1);
+  lc->scan_pts[(size_t)first].assign(points_m, points_m + 2 * (size_t)n_points);
   *id = first;
   return CSM_OK;
 }
@@ -389,6 +402,10 @@ int csm_loop_closure_set_submaps_chains(csm_loop_closure* lc, const csm_chain_ma
   lc->lo.swap(lo);
   lc->hi.swap(hi);
   lc->resolution = mp->resolution;
+  lc->size_x = mp->size_x;
+  lc->size_y = mp->size_y;
+  lc->stack_offset[0] = map_offset[0];
+  lc->stack_offset[1] = map_offset[1];
   lc->offsets.resize(2 * (size_t)n_submaps);
   for (int32_t i = 0; i < n_submaps; ++i) {
     lc->offsets[2 * (size_t)i] = map_offset[0];
@@ -712,15 +729,11 @@ int csm_loop_closure_match_gated(csm_loop_closure* lc, const double* pts, int32_
   return lc_match_gated_locked(lc, pts, n_points, param, pose_world, min_response, results, capacity, n_pass);
 }
 
-int csm_loop_closure_match_gated_full(csm_loop_closure* lc, const double* pts, int32_t n_points, const csm_param* param,
+// csm_loop_closure_match_gated_full with lc->mu held.
+static int lc_match_gated_full_locked(csm_loop_closure* lc, const double* pts, int32_t n_points, const csm_param* param,
                                       const double pose_world[3], double min_response,
                                       csm_loop_closure_result* results, int32_t capacity, int32_t* n_pass, double* covs,
                                       csm_match_result* matches) {
-  if (!lc || !pts || !param || !pose_world || !n_pass || capacity < 0 ||
-      (capacity > 0 && (!results || !covs || !matches)) || !(min_response == min_response))
-    return CSM_ERR_INVALID_ARG;
-  if (param->type == CSM_FAST) return CSM_ERR_INVALID_ARG;
-  std::lock_guard<std::mutex> lk(lc->mu);
   int st = lc_match_gated_locked(lc, pts, n_points, param, pose_world, min_response, results, capacity, n_pass);
   if (st != CSM_OK) return st;
   // each passing submap's device finishes that window: the devices in
@@ -742,6 +755,19 @@ int csm_loop_closure_match_gated_full(csm_loop_closure* lc, const double* pts, i
   for (int r = 0; r < G; ++r)
     if (status[(size_t)r] != CSM_OK) return lc->fail(status[(size_t)r], errs[(size_t)r]);
   return CSM_OK;
+}
+
+int csm_loop_closure_match_gated_full(csm_loop_closure* lc, const double* pts, int32_t n_points, const csm_param* param,
+                                      const double pose_world[3], double min_response,
+                                      csm_loop_closure_result* results, int32_t capacity, int32_t* n_pass, double* covs,
+                                      csm_match_result* matches) {
+  if (!lc || !pts || !param || !pose_world || !n_pass || capacity < 0 ||
+      (capacity > 0 && (!results || !covs || !matches)) || !(min_response == min_response))
+    return CSM_ERR_INVALID_ARG;
+  if (param->type == CSM_FAST) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(lc->mu);
+  return lc_match_gated_full_locked(lc, pts, n_points, param, pose_world, min_response, results, capacity, n_pass, covs,
+                                    matches);
 }
 
 int csm_loop_closure_map_check(csm_loop_closure* lc, csm_gridmap* pub_map, int32_t scan_id,
@@ -767,6 +793,156 @@ int csm_loop_closure_map_check(csm_loop_closure* lc, csm_gridmap* pub_map, int32
                                           nullptr);
   if (st != CSM_OK) return lc->fail(st, std::string("map check: ") + csm_gridmap_last_error(pub_map));
   return CSM_OK;
+}
+
+// SlamProcessor::ScanMatchInterface for every gated submap (csm_loop_closure.h). The rules around
+// the correlative levels -- the box, the start pose, the mean, the penalty and the clamp -- are
+// csm_lc_interface.hpp's.
+int csm_loop_closure_scan_match(csm_loop_closure* lc, csm_gridmap* pub_map, int32_t scan_id,
+                                const csm_loop_closure_interface_param* param, const double pose_world[3],
+                                const double cov_init[9], csm_loop_closure_interface_result* results,
+                                int32_t capacity, int32_t* n_pass) {
+  if (!lc || !param || !pose_world || !n_pass || capacity < 0 || (capacity > 0 && !results) ||
+      !(param->min_response == param->min_response))
+    return CSM_ERR_INVALID_ARG;
+  for (int l = 0; l < 3; ++l)
+    if (param->levels[l].type == CSM_FAST) return CSM_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(lc->mu);
+  if (scan_id < 0 || (size_t)scan_id >= lc->scan_pts.size())
+    return lc->fail(CSM_ERR_INVALID_ARG, "scan match: no kept scan of that id");
+  size_t map_dev = 0;
+  if (param->use_map_check) {
+    if (!pub_map) return lc->fail(CSM_ERR_INVALID_ARG, "scan match: use_map_check without a pub map");
+    csm::GridMapView view;
+    const int vst = csm::gridmap_view(pub_map, &view);
+    if (vst != CSM_OK) return lc->fail(vst, "scan match: the pub map gave no view");
+    while (map_dev < lc->devices.size() && lc->devices[map_dev] != view.device) ++map_dev;
+    if (map_dev == lc->devices.size())
+      return lc->fail(CSM_ERR_INVALID_ARG, "scan match: the pub map lives on device " + std::to_string(view.device) +
+                                               ", which is none of the loop closure's");
+  }
+  if (lc->n_submaps == 0) return lc->fail(CSM_ERR_NO_GRID, "no submaps set");
+  const int32_t levels_run = param->use_fine_scan_match ? 3 : 1;
+  // MapSizeCheck (scan_matchers.h:195-199) for every submap, before anything is launched: a submap
+  // cannot grow here
+  for (int32_t i = 0; i < lc->n_submaps; ++i) {
+    const csm::InterfaceBox box = csm::interface_box(lc->resolution, &lc->offsets[2 * (size_t)i], pose_world,
+                                                     param->range_max, param->levels[0].search_space_size);
+    if (!csm::interface_box_fits(box, lc->size_x, lc->size_y))
+      return lc->fail(CSM_ERR_UNSUPPORTED,
+                      "scan match: MapSizeCheck would grow submap " + std::to_string(i) + " (" +
+                          std::to_string(lc->size_x) + " x " + std::to_string(lc->size_y) + " cells); a submap of " +
+                          std::to_string(csm::interface_size_that_fits(box, lc->size_x, lc->size_y)) +
+                          " cells a side, centred the same, would have fit");
+    // the fine levels convert poses with the stack's one geometry
+    if (levels_run == 3 && (lc->offsets[2 * (size_t)i] != lc->stack_offset[0] ||
+                            lc->offsets[2 * (size_t)i + 1] != lc->stack_offset[1]))
+      return lc->fail(CSM_ERR_UNSUPPORTED, "scan match: submap " + std::to_string(i) +
+                                               "'s offset is not the one its stack was set with (csm_map_info)");
+  }
+  // the query: CreateFrom(raw, 1 / resolution) (sensor_data_manager.h:99-115), rounded once
+  const std::vector<double>& raw = lc->scan_pts[(size_t)scan_id];
+  const int32_t n_points = (int32_t)(raw.size() / 2);
+  const double factor = 1 / lc->resolution;
+  std::vector<double> pts(raw.size());
+  for (size_t i = 0; i < raw.size(); ++i) pts[i] = raw[i] * factor;
+
+  // level 0: the gate and each passer's finish, as csm_loop_closure_match_gated_full
+  // (no more entries than submaps can come back, whatever the caller's capacity)
+  if (capacity > lc->n_submaps) capacity = lc->n_submaps;
+  std::vector<csm_loop_closure_result> wide((size_t)capacity);
+  std::vector<csm_match_result> wide_match((size_t)capacity);
+  std::vector<double> covs((size_t)capacity * 9);
+  static const double kIdentity[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  for (int32_t k = 0; k < capacity; ++k) std::memcpy(&covs[(size_t)9 * k], cov_init ? cov_init : kIdentity, sizeof(kIdentity));
+  int st = lc_match_gated_full_locked(lc, pts.data(), n_points, &param->levels[0], pose_world, param->min_response,
+                                      wide.data(), capacity, n_pass, covs.data(), wide_match.data());
+  if (st != CSM_OK) return st;
+  const int32_t m = *n_pass < capacity ? *n_pass : capacity;
+  std::vector<double> poses((size_t)m * 3), resp((size_t)m * 3, 0.0);
+  for (int32_t k = 0; k < m; ++k) {
+    csm::interface_start_pose(wide_match[(size_t)k].accepted, wide[(size_t)k].pose_world, pose_world, &poses[(size_t)3 * k]);
+    resp[(size_t)3 * k] = wide_match[(size_t)k].response;
+  }
+  // levels 1 and 2: each device's passers in one seeded call on its context, the devices concurrently
+  const int G = (int)lc->devices.size();
+  if (levels_run == 3 && m > 0) {
+    std::vector<int> status((size_t)G, CSM_OK);
+    std::vector<std::string> errs((size_t)G);
+    auto run = [&](int r) {
+      std::vector<int32_t> who, local;
+      for (int32_t k = 0; k < m; ++k)
+        if (lc_owner(lc, wide[(size_t)k].submap) == r) {
+          who.push_back(k);
+          local.push_back(wide[(size_t)k].submap - lc->lo[(size_t)r]);
+        }
+      const size_t n = who.size();
+      if (n == 0) return;
+      std::vector<double> gpts(n * pts.size()), gposes(n * 3), gcovs(n * 9), seed(n), scores(n, 0.0), lresp(2 * n, 0.0);
+      std::vector<int64_t> goff(n + 1, 0);
+      for (size_t j = 0; j < n; ++j) {
+        const size_t k = (size_t)who[j];
+        std::memcpy(gpts.data() + j * pts.size(), pts.data(), pts.size() * sizeof(double));
+        goff[j + 1] = goff[j] + n_points;
+        std::memcpy(&gposes[3 * j], &poses[3 * k], 3 * sizeof(double));
+        std::memcpy(&gcovs[9 * j], &covs[9 * k], 9 * sizeof(double));
+        seed[j] = resp[3 * k];
+      }
+      const int rc = csmh::scan_matchers_batch_grids_levels(lc->ctx[(size_t)r], (int32_t)n, gpts.data(), goff.data(),
+                                                            local.data(), param->levels, 1, 1, seed.data(),
+                                                            gposes.data(), gcovs.data(), scores.data(), lresp.data());
+      if (rc != CSM_OK) {
+        status[(size_t)r] = rc;
+        errs[(size_t)r] = "device " + std::to_string(lc->devices[(size_t)r]) + ": " + csm_last_error(lc->ctx[(size_t)r]);
+        return;
+      }
+      for (size_t j = 0; j < n; ++j) {
+        const size_t k = (size_t)who[j];
+        std::memcpy(&poses[3 * k], &gposes[3 * j], 3 * sizeof(double));
+        std::memcpy(&covs[9 * k], &gcovs[9 * j], 9 * sizeof(double));
+        resp[3 * k + 1] = lresp[j];
+        resp[3 * k + 2] = lresp[n + j];
+      }
+    };
+    DeviceRestore restore;
+    if (!lc->workers) lc->workers.reset(new ShardWorkers(G));
+    lc->workers->run(run);
+    for (int r = 0; r < G; ++r)
+      if (status[(size_t)r] != CSM_OK) return lc->fail(status[(size_t)r], errs[(size_t)r]);
+  }
+  // MapCheckPenalize at every entry's final pose, one launch (as csm_loop_closure_map_check)
+  std::vector<double> penalty((size_t)m, 1.0);
+  if (param->use_map_check && m > 0) {
+    std::vector<int32_t> ids((size_t)m, scan_id);
+    DeviceRestore restore;
+    st = csm_gridmap_feedback_penalty_store(pub_map, lc->stores[map_dev], m, ids.data(), poses.data(), &param->check,
+                                            penalty.data(), nullptr);
+    if (st != CSM_OK) return lc->fail(st, std::string("scan match: map check: ") + csm_gridmap_last_error(pub_map));
+  }
+  for (int32_t k = 0; k < m; ++k) {
+    csm_loop_closure_interface_result& R = results[k];
+    R = csm_loop_closure_interface_result{};
+    R.submap = wide[(size_t)k].submap;
+    R.levels_run = levels_run;
+    std::memcpy(R.pose, &poses[(size_t)3 * k], sizeof(R.pose));
+    std::memcpy(R.cov, &covs[(size_t)9 * k], sizeof(R.cov));
+    std::memcpy(R.response, &resp[(size_t)3 * k], sizeof(R.response));
+    R.map_penalty = penalty[(size_t)k];
+    R.score = csm::interface_score(csm::interface_mean(R.response, levels_run), R.map_penalty);
+    R.wide = wide[(size_t)k];
+    R.wide_match = wide_match[(size_t)k];
+  }
+  return CSM_OK;
+}
+
+int csm_loop_closure_matcher(csm_loop_closure* lc, int32_t shard, csm_ctx** ctx) {
+  if (!lc || !ctx || shard < 0 || (size_t)shard >= lc->ctx.size()) return CSM_ERR_INVALID_ARG;
+  *ctx = lc->ctx[(size_t)shard];
+  return CSM_OK;
+}
+
+double csm_loop_closure_wide_gate(double threshold, int32_t levels_run) {
+  return csm::interface_wide_gate(threshold, levels_run);
 }
 
 }  // extern "C"

@@ -114,6 +114,9 @@ int job_handoff(csm_ctx* c, PipeJob& J, int l, int h) {
                            split);
   });
   c->profiling = timed;
+  // level l's responses of this part: the next level overwrites them when it completes
+  if (st == CSM_OK && J.level_resp)
+    for (int s = s0; s < s0 + J.count[h]; ++s) J.level_resp[(size_t)l * J.n_scans + s] = J.resp[(size_t)s];
   return st;
 }
 
@@ -143,6 +146,7 @@ void job_setup(csm_ctx* c, PipeJob& J, int32_t n_scans, const int64_t* offsets, 
   J.covs = covs;
   J.sum = sum;
   J.scores = nullptr;
+  J.level_resp = nullptr;
   J.pending = false;
   J.last_handoff_done = false;
   // part 0 takes part0_permille of the scans, the others split the rest: a
@@ -226,6 +230,8 @@ int job_finish(csm_ctx* c, PipeJob& J) {
         CSM_OK)
       return st;
     for (int s = s0; s < s0 + J.count[h]; ++s) J.sum[(size_t)s] += J.resp[(size_t)s];
+    if (J.level_resp)
+      for (int s = s0; s < s0 + J.count[h]; ++s) J.level_resp[(size_t)last * J.n_scans + s] = J.resp[(size_t)s];
   }
   if (J.scores)
     for (int s = 0; s < J.n_scans; ++s) J.scores[s] = J.sum[(size_t)s] / J.n_levels;  // :281
@@ -309,11 +315,12 @@ void pipe_free(csm_ctx* c) {
 // (level_end_begin). Scans are independent, so the split changes no result.
 int match_levels_pipelined(csm_ctx* c, int32_t n_scans, const int64_t* offsets, const csm_param* levels,
                            int n_levels, double* poses, double* covs, double* sum,
-                           const int32_t* scan_grid) {
+                           const int32_t* scan_grid, double* level_resp) {
   const int K = std::max(2, std::min(c->pipeline_parts, csm_ctx::kMaxParts));
   PipeMode mode(c);
   PipeJob& J = pipe_of(c).job[0];
   job_setup(c, J, n_scans, offsets, levels, n_levels, poses, covs, sum, scan_grid, K, 0);
+  J.level_resp = level_resp;
   int st;
   for (int h = 0; h < K; ++h)
     if ((st = job_begin(c, J, h)) != CSM_OK) return pipe_abort(c, st);

@@ -56,7 +56,7 @@ EXPORTED = (
     "csm_loop_closure_set_submaps", "csm_loop_closure_match", "csm_loop_closure_match_full",
     "csm_loop_closure_match_gated", "csm_loop_closure_match_gated_full",
     "csm_loop_closure_add_scan", "csm_loop_closure_set_scan_pose", "csm_loop_closure_set_submaps_chains",
-    "csm_loop_closure_map_check",
+    "csm_loop_closure_map_check", "csm_loop_closure_scan_match", "csm_loop_closure_matcher", "csm_loop_closure_wide_gate",
     # include/csm_map_check.h
     "csm_gridmap_feedback_penalty_batch", "csm_gridmap_feedback_penalty_store", "csm_gridmap_map_check_launches",
     "csm_gridmap_feedback_penalty_store_kernel_ms",
@@ -268,6 +268,33 @@ class CsmMapCheckParam(C.Structure):
     ]
 
 
+class CsmLoopClosureInterfaceParam(C.Structure):
+    """csm_loop_closure_interface_param (include/csm_loop_closure.h)."""
+    _fields_ = [
+        ("levels", CsmParam * 3),
+        ("use_fine_scan_match", C.c_int32),
+        ("use_map_check", C.c_int32),
+        ("range_max", C.c_double),
+        ("min_response", C.c_double),
+        ("check", CsmMapCheckParam),
+    ]
+
+
+class CsmLoopClosureInterfaceResult(C.Structure):
+    """csm_loop_closure_interface_result (include/csm_loop_closure.h)."""
+    _fields_ = [
+        ("submap", C.c_int32),
+        ("levels_run", C.c_int32),
+        ("pose", C.c_double * 3),
+        ("cov", C.c_double * 9),
+        ("score", C.c_double),
+        ("response", C.c_double * 3),
+        ("map_penalty", C.c_double),
+        ("wide", CsmLoopClosureResult),
+        ("wide_match", CsmMatchResult),
+    ]
+
+
 class CsmOptimizeParam(C.Structure):
     """csm_optimize_param == OptimizeScanMatchParam (optimize_scan_matcher.h:33-58)."""
 
@@ -473,6 +500,11 @@ def _bind(lib: C.CDLL) -> C.CDLL:
                                                           _i32p, _dp]),
         "csm_loop_closure_map_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CsmMapCheckParam),
                                                  C.POINTER(CsmLoopClosureResult), C.c_int32, _dp]),
+        "csm_loop_closure_scan_match": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32,
+                                                  C.POINTER(CsmLoopClosureInterfaceParam), _dp, _dp,
+                                                  C.POINTER(CsmLoopClosureInterfaceResult), C.c_int32, _i32p]),
+        "csm_loop_closure_wide_gate": (C.c_double, [C.c_double, C.c_int32]),
+        "csm_loop_closure_matcher": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
         "csm_gridmap_feedback_penalty_batch": (C.c_int, [C.c_void_p, C.c_int32, _dp, _i64p, C.c_int32, _i32p, _dp,
                                                          C.POINTER(CsmMapCheckParam), _dp, _i32p]),
         "csm_gridmap_feedback_penalty_store": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, _i32p, _dp,

@@ -159,7 +159,11 @@ class DeviceLoopClosure:
         self._grids = g  # resident by host pointer: keep alive
         off = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1, 2)
         assert off.shape[0] == g.shape[0]
-        info = CsmMapInfo(float(resolution), 0.0, 0.0, g.shape[2], g.shape[1], 0, 0)
+        # the stack's own geometry carries the submaps' offset when they share one (what the level
+        # drivers behind scan_match convert poses with; the searches take centres in map cells)
+        same = bool(off.shape[0]) and bool(np.all(off == off[0]))
+        info = CsmMapInfo(float(resolution), float(off[0, 0]) if same else 0.0, float(off[0, 1]) if same else 0.0,
+                          g.shape[2], g.shape[1], 0, 0)
         self._check(self._lib.csm_loop_closure_set_submaps(self._h, g.ctypes.data_as(C.c_void_p), g.shape[0],
                                                            C.byref(info), off.ctypes.data_as(C.POINTER(C.c_double)),
                                                            int(version)))
@@ -305,6 +309,59 @@ class DeviceLoopClosure:
         self._check(self._lib.csm_loop_closure_map_check(self._h, pub_map.handle, int(scan_id), C.byref(prm), res, n,
                                                          out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
+
+    def scan_match(self, pub_map, scan_id: int, levels, pose_world, min_response: float, capacity: int,
+                   range_max: float, use_fine_scan_match: bool = True, check=None, cov_init=None):
+        """csm_loop_closure_scan_match: ScanMatchInterface's result (slam_processor.cpp:250-326) for
+        every submap whose level-0 best is >= min_response -> (list of dicts in ascending submap
+        order, at most `capacity`; n_pass). levels: the three CorrelationScanMatchParam of the call;
+        check: None (no map check, pub_map may be None) or (check_point_num, bound_tolerance,
+        penalty_gain[, use_blur[, use_logistic]]), the logistic on by default as ScanMatchInterface
+        passes it. Each dict: submap, levels_run, pose (3,), cov (3, 3), score, response (3,),
+        map_penalty, wide (LoopClosureResult), wide_pose_world, wide_match (as Context.search_match)."""
+        from . import _as_param, match_result_dict
+        from ._abi import CsmLoopClosureInterfaceParam, CsmLoopClosureInterfaceResult, CsmMapCheckParam
+        C = self._C
+        prm = CsmLoopClosureInterfaceParam()
+        for k in range(3):
+            prm.levels[k] = _as_param(levels[k])
+        prm.use_fine_scan_match = int(bool(use_fine_scan_match))
+        prm.use_map_check = int(check is not None)
+        prm.range_max = float(range_max)
+        prm.min_response = float(min_response)
+        if check is not None:
+            c = tuple(check) + (False, True)[len(check) - 3:] if len(check) < 5 else tuple(check)
+            prm.check = CsmMapCheckParam(int(c[0]), int(bool(c[3])), int(bool(c[4])), 0, float(c[1]), float(c[2]))
+        pose = np.ascontiguousarray(pose_world, dtype=np.float64)
+        assert pose.size == 3
+        dp = C.POINTER(C.c_double)
+        cov_p = None
+        if cov_init is not None:
+            cov0 = np.ascontiguousarray(cov_init, dtype=np.float64).reshape(9)
+            cov_p = cov0.ctypes.data_as(dp)
+        cap = int(capacity)
+        res = (CsmLoopClosureInterfaceResult * max(cap, 1))()
+        n = C.c_int32(-1)
+        self._check(self._lib.csm_loop_closure_scan_match(
+            self._h, pub_map.handle if pub_map is not None else None, int(scan_id), C.byref(prm),
+            pose.ctypes.data_as(dp), cov_p, res if cap > 0 else None, cap, C.byref(n)))
+        out = []
+        for k in range(max(0, min(int(n.value), cap))):
+            r, w = res[k], res[k].wide
+            out.append({"submap": int(r.submap), "levels_run": int(r.levels_run), "pose": np.array(r.pose[:]),
+                        "cov": np.array(r.cov[:]).reshape(3, 3), "score": float(r.score),
+                        "response": np.array(r.response[:]), "map_penalty": float(r.map_penalty),
+                        "wide": LoopClosureResult(w.score, w.global_index, w.submap, w.x, w.y, w.angle),
+                        "wide_pose_world": np.array(w.pose_world[:]), "wide_match": match_result_dict(r.wide_match)})
+        return out, int(n.value)
+
+    def matcher(self, shard: int):
+        """The matcher context of device `shard` of the handle, borrowed (csm_set_profiling /
+        kernel_stats around a call)."""
+        from . import Context
+        h = self._C.c_void_p()
+        self._check(self._lib.csm_loop_closure_matcher(self._h, int(shard), self._C.byref(h)))
+        return Context.borrow(h, self)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
