@@ -2,10 +2,11 @@
 // fixed-point grid (the palette index grid and its values, the pair kernel's
 // strip copies of it, the maps of uniform boxes, the phase kernel's strip
 // copies of gridi): the record that holds them, the key that says whether they
-// are of the current grid, and the rules that say which are built and used,
+// are of the current grid, the rules that say which are built and used, and
+// the layouts' geometry (how large gridi and each copy are for a grid size),
 // as pure host arithmetic (no HIP, no context). csm_grid.cpp builds the copies
-// and turns them into LevelWork fields; tests/test_grid_copies.py compiles
-// this header into a stand-alone program.
+// and turns them into LevelWork fields; tests/test_grid_copies.py and
+// tests/test_grid_geom.py compile this header into stand-alone programs.
 #pragma once
 #include <cstdint>
 
@@ -43,6 +44,81 @@ inline bool phase_wants_palette(bool phase_strips, bool pair_kernel, int bg_runs
   return phase_strips && pair_kernel && bg_runs != 0;
 }
 
+// ---- The layouts' geometry -------------------------------------------------
+// How large gridi and each copy are, from the grid's size alone. The kernels
+// that read them (csm_box.hip, csm_phase.hip, csm_tiny.hip) and the builders
+// (csm_gridprep.hip, csm_palette.hip) all take their sizes from here;
+// tests/cpp/grid_geom_check.cpp walks every read pattern the kernels document
+// over a range of grid sizes and checks that none leaves these sizes.
+
+// gridi layout: row pitch = round4(size_x + kGridiPadCols) cells, size_y +
+// kGridiPadRows rows; every cell outside [0,size_x) x [0,size_y) is zero, so a
+// 16 x 16 box whose corner lies on the grid never leaves the buffer.
+constexpr int kGridiPadCols = 15;
+constexpr int kGridiPadRows = 16;
+constexpr int32_t gridi_pitch(int32_t sx) { return (sx + kGridiPadCols + 3) & ~3; }
+
+// The pair kernel's strip copies of the palette index grid: kStripCopies
+// copies, each kStripShift cells further along, in strips kStripW bytes wide
+// (csm_internal.hpp says why).
+constexpr int kStripW = 16;
+#ifndef CSM_STRIP_COPIES
+#define CSM_STRIP_COPIES 16
+#endif
+constexpr int kStripCopies = CSM_STRIP_COPIES;
+constexpr int kStripShift = kStripW / kStripCopies;
+static_assert(kStripCopies == 4 || kStripCopies == 16, "strip copies: 4 or 16");
+constexpr int kStripPadRows = 16;  // zero rows below the grid (box rows and the zero run's rows)
+constexpr int kStripPadLo = 16;    // columns and rows before the grid's first
+struct StripGeom {
+  int32_t rows, n_strips;
+  int64_t strip_bytes, copy_bytes, grid_bytes;
+};
+inline StripGeom strip_geom(int size_x, int size_y) {
+  StripGeom G{};
+  G.rows = kStripPadLo + size_y + kStripPadRows;
+  // a box row piece starts at (ix & ~(S - 1)) + S c <= kStripPadLo + size_x - 1 + 16 - S
+  // in copy c (S = kStripShift, ix the padded column)
+  G.n_strips = (kStripPadLo + size_x + 15 - kStripShift) / kStripW + 1;
+  G.strip_bytes = (int64_t)G.rows * kStripW;
+  G.copy_bytes = G.strip_bytes * G.n_strips;
+  G.grid_bytes = G.copy_bytes * kStripCopies;
+  return G;
+}
+
+// The maps of uniform boxes: one bit per padded box corner, 8 x 8 corners to a
+// 64-bit word.
+struct BgGeom {
+  int32_t tiles_x, tiles_y;
+  int64_t grid_bytes;
+};
+inline BgGeom bg_geom(int size_x, int size_y) {
+  BgGeom G{};
+  // corners 0 .. kStripPadLo + size - 1 per axis (the box test's in-grid range)
+  G.tiles_x = (kStripPadLo + size_x + 7) / 8;
+  G.tiles_y = (kStripPadLo + size_y + 7) / 8;
+  G.grid_bytes = (int64_t)G.tiles_x * G.tiles_y * 8;
+  return G;
+}
+
+// The phase kernel's strip copies of gridi: kIStripCopies copies, each 4 cells
+// further along, in strips of kIStripCells cells.
+constexpr int kIStripCells = 8;
+constexpr int kIStripCopies = 2;
+constexpr int kIStripPadRows = 16;
+constexpr int kIStripPadLo = 16;
+inline StripGeom istrip_geom(int size_x, int size_y) {
+  StripGeom G{};
+  G.rows = kIStripPadLo + size_y + kIStripPadRows;
+  // a box row starts at cell (ix & ~3) + 4c <= kIStripPadLo + size_x - 1 + 4 in
+  // copy c (ix the padded column), phase <= 3
+  G.n_strips = (kIStripPadLo + size_x + 3) / kIStripCells + 1;
+  G.strip_bytes = (int64_t)G.rows * kIStripCells * 4;
+  G.copy_bytes = G.strip_bytes * G.n_strips;
+  G.grid_bytes = G.copy_bytes * kIStripCopies;
+  return G;
+}
+
 // What a family of copies was built from: the grid generation (csm_ctx::grid_gen)
 // and the fixed-point grid itself.
 struct CopyKey {
@@ -63,7 +139,7 @@ struct GridCopiesOf {
   int32_t pal_n = 0;  // palette size (0: none, e.g. more than kPalMax values)
   Buf pal_strips;     // strip copies of pal_grid (v11 pair kernel; palettes of <= kPairMaxPal values)
   bool pal_strips_ok = false;
-  // The pair kernel's map of uniform boxes (csm_palette.hip bg_geom), built
+  // The pair kernel's map of uniform boxes (bg_geom above), built
   // with the strips and keyed like them. bg_ok: the pair kernel uses it
   // (bg_map_used).
   Buf bg_map, bg_info;

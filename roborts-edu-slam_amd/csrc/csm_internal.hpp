@@ -6,6 +6,7 @@
 #include <hip/hip_runtime_api.h>
 #include <cstdint>
 
+#include "csm_grid_copies.hpp"
 #include "csm_optimize_step.hpp"
 
 namespace csm {
@@ -190,7 +191,7 @@ struct LevelWork {
   const int32_t* pal_vals;
   int64_t pal_stride;
   // The strip copies of the palette grid (score_box_pair_kernel, pal_n <=
-  // kPairMaxPal; csm_palette.hip strip_geom): bytes per strip, per copy and
+  // kPairMaxPal; csm_grid_copies.hpp strip_geom): bytes per strip, per copy and
   // per grid of the stack.
   const uint8_t* pal_strips;
   int32_t strip_bytes;
@@ -207,7 +208,7 @@ struct LevelWork {
   // the largest n_used of the level's windows (0: unknown); the pair kernel
   // takes its run-free form at or below kPairNoRunBeams (csm_box.hip)
   int32_t max_n_used;
-  // The map of uniform boxes (score_box_pair_kernel; csm_palette.hip bg_geom):
+  // The map of uniform boxes (score_box_pair_kernel; csm_grid_copies.hpp bg_geom):
   // bit (ix0, iy0) set when the whole kPalMaxSpace^2 box from that padded
   // corner holds the grid's background index, which bg_info names per grid of
   // the stack (kBgInfoBg). Such a beam adds the same value to every candidate:
@@ -440,18 +441,14 @@ hipError_t launch_build_palette(const int32_t* gridi, int64_t n, int32_t* scratc
 // box row piece is one aligned 16-byte strip row and a box's 13 rows are 208
 // contiguous bytes (2.5 cache lines, not 13-14).
 constexpr int kPairMaxPal = 16;
-constexpr int kStripW = 16;
-#ifndef CSM_STRIP_COPIES
-#define CSM_STRIP_COPIES 16
-#endif
+using csmh::kStripW;
 // copies of the index grid, each kStripShift cells further along: 16 puts
 // every box row at byte 0 of its strip row (64 MB for a 2000^2 grid); 4
 // leaves a byte phase ix0 & 3 the kernel aligns (v_alignbyte, 16 MB). r04,
 // isolated coarse launch of 4096 windows: 1.404 ms with 4, 1.358 with 16.
-constexpr int kStripCopies = CSM_STRIP_COPIES;
-constexpr int kStripShift = kStripW / kStripCopies;
-static_assert(kStripCopies == 4 || kStripCopies == 16, "strip copies: 4 or 16");
-constexpr int kStripPadRows = 16;  // zero rows below the grid (box rows and the zero run's rows)
+using csmh::kStripCopies;
+using csmh::kStripShift;
+using csmh::kStripPadRows;  // zero rows below the grid (box rows and the zero run's rows)
 // Columns and rows before the grid's first (pair strips): column -1 repeats
 // column 0 and row -1 row 0, the rest hold index 0 (the outside value). The
 // reference truncates toward zero, so a cell coordinate t in (-1, 0) reads
@@ -460,12 +457,10 @@ constexpr int kStripPadRows = 16;  // zero rows below the grid (box rows and the
 // reads, and a beam whose box straddles the grid's low edge stays on the fast
 // path (r05: 10 % of the headline's waves had such beams, 0.8 % of beams,
 // each summed cell by cell before).
-constexpr int kStripPadLo = 16;
-struct StripGeom {
-  int32_t rows, n_strips;
-  int64_t strip_bytes, copy_bytes, grid_bytes;
-};
-StripGeom strip_geom(int size_x, int size_y);
+using csmh::kStripPadLo;
+// (the geometry itself: csm_grid_copies.hpp)
+using csmh::StripGeom;
+using csmh::strip_geom;
 // idx: the palette index grid(s) (row pitch `pitch` bytes, idx_stride bytes
 // per grid); out: n_grids * strip_geom().grid_bytes bytes.
 hipError_t launch_build_strips(const uint8_t* idx, int pitch, int size_x, int size_y, int64_t idx_stride,
@@ -480,11 +475,8 @@ bool box_pair_supported(int ns);
 // hold it in the padded image the strips are made from. Bits lie in 8 x 8
 // tiles, one 64-bit word each, byte iy0 & 7 of the word holding row iy0's
 // eight corners: a chunk's beams walk along a wall and share words and lines.
-struct BgGeom {
-  int32_t tiles_x, tiles_y;
-  int64_t grid_bytes;
-};
-BgGeom bg_geom(int size_x, int size_y);
+using csmh::BgGeom;
+using csmh::bg_geom;
 // info: kBgInfoInts ints per grid, zeroed by the launcher: the histogram of
 // the in-grid cells' indices, then the background index and the set bits.
 // out: the kPalMaxSpace^2 map (kBgInfoSet counts its bits); out5: the map of
@@ -497,15 +489,15 @@ hipError_t launch_build_bg_map(const uint8_t* idx, int pitch, int size_x, int si
 // cell x of row y at cell x + 4c of its strip row, strips kIStripCells cells
 // (32 bytes) wide with their rows contiguous, so a 5 x 5 phase box (corner
 // phase <= 3 cells, two 16-byte pieces per row) is 160 contiguous bytes.
-constexpr int kIStripCells = 8;
-constexpr int kIStripCopies = 2;
-constexpr int kIStripPadRows = 16;
+using csmh::kIStripCells;
+using csmh::kIStripCopies;
+using csmh::kIStripPadRows;
 // columns and rows before the grid's first in the phase strips, as
 // kStripPadLo for the pair strips (column -1 repeats column 0, row -1 row 0,
 // the rest outside): a box straddling the low edge stays on the fast path
 // (r05: 6 % of the headline's fine-level waves summed such beams cell by cell)
-constexpr int kIStripPadLo = 16;
-StripGeom istrip_geom(int size_x, int size_y);
+using csmh::kIStripPadLo;
+using csmh::istrip_geom;
 hipError_t launch_build_istrips(const int32_t* gridi, int pitch, int size_x, int size_y, int64_t gridi_stride,
                                 int n_grids, int32_t* out, hipStream_t stream);
 hipError_t launch_score_box_pair(const LevelWork& L, const ScanWork* d_scans, const double* d_pts,
@@ -566,12 +558,13 @@ hipError_t launch_angle_trig(AngleEntry* d_rows, int64_t n, const double* d_tab,
 // every θ inside the restated domain (the caller checks).
 hipError_t launch_angle_rows(const ScanWork* d_sw, int nw, int n_angles, double offset, double ares, AngleEntry* d_rows,
                              const double* d_tab, hipStream_t stream);
-// gridi layout: row pitch = round4(size_x + kGridiPadCols) cells, size_y +
-// kGridiPadRows rows; every cell outside [0,size_x) x [0,size_y) is zero, so a
-// 16 x 16 box whose corner lies on the grid never leaves the buffer.
-constexpr int kGridiPadCols = 15;
-constexpr int kGridiPadRows = 16;
-constexpr int32_t gridi_pitch(int32_t sx) { return (sx + kGridiPadCols + 3) & ~3; }
+// gridi layout (csm_grid_copies.hpp): row pitch = round4(size_x +
+// kGridiPadCols) cells, size_y + kGridiPadRows rows; every cell outside
+// [0,size_x) x [0,size_y) is zero, so a 16 x 16 box whose corner lies on the
+// grid never leaves the buffer.
+using csmh::kGridiPadCols;
+using csmh::kGridiPadRows;
+using csmh::gridi_pitch;
 // Grid statistics for the exact integer path (csm_set_grid; csm_gridprep.hip).
 struct GridStats {
   int32_t min_gexp;       // every nonzero |v| is a multiple of 2^min_gexp

@@ -311,17 +311,8 @@ __global__ __launch_bounds__(256) void istrips_kernel(const int32_t* __restrict_
 
 }  // namespace
 
-StripGeom istrip_geom(int size_x, int size_y) {
-  StripGeom G{};
-  G.rows = kIStripPadLo + size_y + kIStripPadRows;
-  // a box row starts at cell (ix & ~3) + 4c <= kIStripPadLo + size_x - 1 + 4 in
-  // copy c (ix the padded column), phase <= 3
-  G.n_strips = (kIStripPadLo + size_x + 3) / kIStripCells + 1;
-  G.strip_bytes = (int64_t)G.rows * kIStripCells * 4;
-  G.copy_bytes = G.strip_bytes * G.n_strips;
-  G.grid_bytes = G.copy_bytes * kIStripCopies;
-  return G;
-}
+// (istrip_geom, strip_geom, bg_geom: the sizes of what these launchers fill,
+// csm_grid_copies.hpp)
 
 hipError_t launch_build_istrips(const int32_t* gridi, int pitch, int size_x, int size_y, int64_t gridi_stride,
                                 int n_grids, int32_t* out, hipStream_t stream) {
@@ -334,18 +325,6 @@ hipError_t launch_build_istrips(const int32_t* gridi, int pitch, int size_x, int
   return hipGetLastError();
 }
 
-StripGeom strip_geom(int size_x, int size_y) {
-  StripGeom G{};
-  G.rows = kStripPadLo + size_y + kStripPadRows;
-  // a box row piece starts at (ix & ~(S - 1)) + S c <= kStripPadLo + size_x - 1 + 16 - S
-  // in copy c (S = kStripShift, ix the padded column)
-  G.n_strips = (kStripPadLo + size_x + 15 - kStripShift) / kStripW + 1;
-  G.strip_bytes = (int64_t)G.rows * kStripW;
-  G.copy_bytes = G.strip_bytes * G.n_strips;
-  G.grid_bytes = G.copy_bytes * kStripCopies;
-  return G;
-}
-
 hipError_t launch_build_strips(const uint8_t* idx, int pitch, int size_x, int size_y, int64_t idx_stride,
                                int n_grids, uint8_t* out, hipStream_t stream) {
   const StripGeom G = strip_geom(size_x, size_y);
@@ -355,15 +334,6 @@ hipError_t launch_build_strips(const uint8_t* idx, int pitch, int size_x, int si
   hipLaunchKernelGGL(pal_strips_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, idx, pitch, size_x, size_y,
                      G.rows, G.n_strips, idx_stride, G.grid_bytes, n_grids, reinterpret_cast<uint4*>(out));
   return hipGetLastError();
-}
-
-BgGeom bg_geom(int size_x, int size_y) {
-  BgGeom G{};
-  // corners 0 .. kStripPadLo + size - 1 per axis (the box test's in-grid range)
-  G.tiles_x = (kStripPadLo + size_x + 7) / 8;
-  G.tiles_y = (kStripPadLo + size_y + 7) / 8;
-  G.grid_bytes = (int64_t)G.tiles_x * G.tiles_y * 8;
-  return G;
 }
 
 hipError_t launch_build_bg_map(const uint8_t* idx, int pitch, int size_x, int size_y, int64_t idx_stride,
